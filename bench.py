@@ -3,9 +3,20 @@
 level that serves its bytes, and the reference's own multithreaded CPU path timed on this
 host beside it.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
-        --master-port P bench.py --gpus N --steps K --warmup W
+        --master-port P bench.py --gpus N --steps K --warmup W [--full]
+
+A plain run does what the headline figure needs and no more: set-up, one counting render (the
+rays of a frame), the warm-up, the K timed steps, and the result line (`value`, `ms_per_step`).
+Everything else -- the one-stream serial rate, the per-kernel times and the roofline, the gather
+and host-frame timings, the predicted part scaling, the ordered closest hit, the K sweep and the
+reference's CPU path -- runs only with `--full` (`--no-cpu-baseline`, `--no-sweep` and
+`--no-extras` narrow a full run).  `--dump-outputs DIR` writes the frames the last timed step
+rendered (DIR/hdr.npy, DIR/ldr.npy, float32; with N ranks DIR/hdr_rank<r>.npy, rank r's rows in a
+zeroed frame; at most 64 MB in all, a seeded sample of the pixels where the frames are larger)
+right after the timed steps; scene, camera and seed are fixed by the arguments, so two builds can
+be compared output for output.
 
 A step = one full 1920x1080 frame (one sample pass) traced and shaded, inputs (scene, BVH)
 resident in HBM.  With N ranks every frame is partitioned (multigpu.py): rank r renders the
@@ -72,6 +83,11 @@ def parse():
     p.add_argument("--inflight", type=int, default=0,
                    help="frames in flight (scene replicas / streams the steps rotate over); 0 = 16, "
                         "1 for c5")
+    p.add_argument("--full", action="store_true",
+                   help="also run everything beside the headline figure: serial rate, per-kernel times and "
+                        "roofline, gather / host-frame / part / ordered timings, the K sweep, the CPU baseline")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the frames of the last timed step as DIR/<name>.npy (float32)")
     return p.parse_args()
 
 
@@ -203,13 +219,13 @@ def cpu_baseline(xml_dir, xml, count_rays, reps, rows=None, kind=None):
 
 
 # ----------------------------------------------------------------------------- timing
-def measure(render, torch, steps, warmup, barrier, serial=None):
+def measure(render, torch, steps, warmup, barrier, serial=None, frame_pass=True):
     """Wall time of exactly `steps` frames between barrier + synchronize on both sides (no
     event records inside the timed loop: they cost ~0.01 ms per frame, tools/diag_streams.py);
     `render(k)` issues step k (with frames in flight, on the stream of replica k % F -- the
     device-wide synchronize waits for all of them).  From a separate untimed pass of
     `serial()` (one replica, one stream) with an event pair around each frame: the mean GPU
-    time of one frame alone."""
+    time of one frame alone (None without `frame_pass`: a plain run times its steps only)."""
     import inspect
     if len(inspect.signature(render).parameters) == 0:
         r0 = render
@@ -233,6 +249,8 @@ def measure(render, torch, steps, warmup, barrier, serial=None):
     torch.cuda.synchronize()
     barrier()
     elapsed = time.perf_counter() - t0
+    if not frame_pass:
+        return elapsed, None
     stream = torch.cuda.current_stream()
     starts = [torch.cuda.Event(enable_timing=True) for _ in range(steps)]
     ends = [torch.cuda.Event(enable_timing=True) for _ in range(steps)]
@@ -448,8 +466,28 @@ def sweep_point(args, torch, rtgpu, local, K, hdr, ldr):
         shutil.rmtree(sub, ignore_errors=True)
 
 
+DUMP_BUDGET = 64 * 1000 * 1000     # bytes --dump-outputs may write in all
+
+
+def dump_outputs(out_dir, frames, writers=1):
+    """--dump-outputs: `frames` (name -> device tensor, pixels x channels) as out_dir/<name>.npy in
+    float32.  A frame over its share of the budget is written as a fixed, seeded sample of its
+    pixels (sorted pixel indices, the same for every run of the same arguments)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BUDGET // (writers * len(frames)) - 4096      # `writers` processes share the budget; the .npy header
+    for name, t in frames.items():
+        a = t.cpu().numpy().astype(np.float32)
+        pixels = a.reshape(-1, a.shape[-1])
+        keep = share // (4 * pixels.shape[1])
+        if pixels.shape[0] > keep:
+            a = pixels[np.sort(np.random.default_rng(0x5EED).choice(pixels.shape[0], size=keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     args = parse()
+    dump_dir = os.path.abspath(args.dump_outputs) if args.dump_outputs else None   # before the chdir below
     import torch
 
     import multigpu
@@ -502,8 +540,9 @@ def main():
         ds = rtgpu.DeviceScene(hs, local)
         cam = hs.camera(0)
         H, W = cam["height"], cam["width"]
-        hdr = torch.empty((H, W, 3), dtype=torch.float32, device=f"cuda:{local}")
-        ldr = torch.empty((H, W, 3), dtype=torch.uint8, device=f"cuda:{local}")
+        # zeroed: with N ranks a rank writes its own rows only, and --dump-outputs writes whole frames
+        hdr = torch.zeros((H, W, 3), dtype=torch.float32, device=f"cuda:{local}")
+        ldr = torch.zeros((H, W, 3), dtype=torch.uint8, device=f"cuda:{local}")
         seed = 0x5EED
         part = (rank, world)
         sptr = torch.cuda.current_stream().cuda_stream
@@ -521,7 +560,7 @@ def main():
         streams = [torch.cuda.Stream() for _ in range(F if F > 1 else 0)]
         reps = [(ds, hdr, ldr, streams[0].cuda_stream if F > 1 else sptr)]
         for k in range(1, F):
-            reps.append((rtgpu.DeviceScene(hs, local), torch.empty_like(hdr), torch.empty_like(ldr),
+            reps.append((rtgpu.DeviceScene(hs, local), torch.zeros_like(hdr), torch.zeros_like(ldr),
                          streams[k].cuda_stream))
 
         def render_step(k):
@@ -540,27 +579,39 @@ def main():
         rays = st["camera_rays"] + st["secondary_rays"] + st["shadow_rays"]
 
         log(f"rays/frame {rays} (this part {part_rays}); timing {args.steps} steps, {F} frames in flight")
-        elapsed, kern_ms = measure(render_step, torch, args.steps, args.warmup, barrier, serial=lambda: render())
+        elapsed, kern_ms = measure(render_step, torch, args.steps, args.warmup, barrier, serial=lambda: render(),
+                                   frame_pass=args.full)
         log(f"timed: {elapsed / args.steps * 1e3:.3f} ms/step")
+        if dump_dir:
+            # the frames of the last timed step (replica (steps - 1) % F; every rank its own rows)
+            _, last_hdr, last_ldr, _ = reps[(args.steps - 1) % F]
+            tag = f"_rank{rank}" if world > 1 else ""
+            dump_outputs(dump_dir, {"hdr" + tag: last_hdr, "ldr" + tag: last_ldr}, writers=world)
+            log(f"outputs of the last step written to {dump_dir}")
         elapsed = reduce_max(elapsed)
-        kern_ms = reduce_max(kern_ms)
         value = rays * args.steps / elapsed / 1e6
-        # the same frames one after another on one stream (no overlap): the single-frame rate
-        s_el, _ = measure(lambda: render(), torch, args.steps, 1, barrier)
-        s_el = reduce_max(s_el)
-
-        ktimes = kernel_times(ds, torch, lambda: render(rtgpu.RTG_RENDER_TIMING), args.steps)
-        # the library times the kernels of the last pass (its samples: several per pass in the
-        # wavefront and ray-tree pipelines): bytes of this rank's pass
-        pass_samples = ds.timed_samples()
-        kbytes = {k: v * pass_samples / max(1, cam["spp"]) for k, v in kernel_bytes(part_st, W, H).items()}
-        dom = max((k for k in ktimes if k in kbytes), key=lambda k: ktimes[k])
         K = int(args.K) if args.config == "headline" else None
-        share = part_rays / max(rays, 1)
-        rl = roofline(dom, kbytes[dom], ktimes[dom], pmc_summary(dom, K, world, share, workload=args.config))
-        rl.update({"kernels_ms": {k: round(v, 4) for k, v in ktimes.items()}, "frame_ms": round(kern_ms, 4),
-                   "frame_algo_bytes": int(kernel_bytes(st, W, H)["frame"]),
-                   "frame_l2_frac": round(kernel_bytes(st, W, H)["frame"] / (kern_ms * 1e-3) / 1e9 / L2_PEAK_GBS, 4)})
+        serial_rate = rl = None
+        if args.full:
+            kern_ms = reduce_max(kern_ms)
+            # the same frames one after another on one stream (no overlap): the single-frame rate
+            s_el, _ = measure(lambda: render(), torch, args.steps, 1, barrier)
+            s_el = reduce_max(s_el)
+            serial_rate = {"ms_per_step": round(s_el / args.steps * 1e3, 4),
+                           "mrays_s": round(rays * args.steps / s_el / 1e6, 2),
+                           "what": "the same steps issued on one stream, each frame after the previous one"}
+
+            ktimes = kernel_times(ds, torch, lambda: render(rtgpu.RTG_RENDER_TIMING), args.steps)
+            # the library times the kernels of the last pass (its samples: several per pass in the
+            # wavefront and ray-tree pipelines): bytes of this rank's pass
+            pass_samples = ds.timed_samples()
+            kbytes = {k: v * pass_samples / max(1, cam["spp"]) for k, v in kernel_bytes(part_st, W, H).items()}
+            dom = max((k for k in ktimes if k in kbytes), key=lambda k: ktimes[k])
+            share = part_rays / max(rays, 1)
+            rl = roofline(dom, kbytes[dom], ktimes[dom], pmc_summary(dom, K, world, share, workload=args.config))
+            rl.update({"kernels_ms": {k: round(v, 4) for k, v in ktimes.items()}, "frame_ms": round(kern_ms, 4),
+                       "frame_algo_bytes": int(kernel_bytes(st, W, H)["frame"]),
+                       "frame_l2_frac": round(kernel_bytes(st, W, H)["frame"] / (kern_ms * 1e-3) / 1e9 / L2_PEAK_GBS, 4)})
         ext = max(rays - st["shadow_rays"], 1)
         result = {
             "metric": METRIC,
@@ -569,6 +620,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": round(elapsed / args.steps * 1e3, 4),
             "higher_is_better": True,
             "scaling": "strong",
@@ -590,15 +642,13 @@ def main():
                 "parallelism": f"image partition x{world}: 8-row bands dealt round-robin rotated one slot per round, rank r "
                                f"renders band k*{world} + ((r - k) mod {world}) (one frame per step)",
                 "frames_in_flight": F,
-                "serial": {"ms_per_step": round(s_el / args.steps * 1e3, 4),
-                           "mrays_s": round(rays * args.steps / s_el / 1e6, 2),
-                           "what": "the same steps issued on one stream, each frame after the previous one"},
+                "serial": serial_rate,
             },
             "roofline": rl,
             "cpu_baseline": None,
         }
 
-        if not args.no_extras:
+        if args.full and not args.no_extras:
             # host framebuffer gather: every rank renders its rows straight into one page-locked
             # shared frame (LDR = what main.cpp saves; + the float frame for a tonemapped camera)
             name = f"rtg_bench_{os.environ.get('MASTER_PORT', str(os.getpid()))}"
@@ -668,7 +718,7 @@ def main():
                             "checked (t, object, face) minimum, the reference walk where the check fails; "
                             "not the headline value (agreement measured, not proven)"}
 
-        if rank == 0 and world == 1 and not args.no_sweep and args.config == "headline":
+        if args.full and rank == 0 and world == 1 and not args.no_sweep and args.config == "headline":
             sweep = {}
             for Ks in SWEEP_K:
                 if Ks == args.K:
@@ -684,7 +734,7 @@ def main():
         # the reference's CPU path on this host, rank 0 only, outside the timed region, at every N
         # (the same frame or row band: its rate does not depend on how the GPUs split it); the
         # rays of the rows it renders from this GPU's counting render of those rows
-        if rank == 0 and not args.no_cpu_baseline:
+        if args.full and rank == 0 and not args.no_cpu_baseline:
             def count_rays(r0, r1):
                 if (r0, r1) == (0, H) and world == 1:
                     return rays

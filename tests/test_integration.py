@@ -1,5 +1,5 @@
 """The drop-in behind the reference's own parser and object model:
-integration/_build/dorkrt loads a scene with DorkTracer::Scene::loadFromXml (the reference's
+oracle/_ref/dorkrt loads a scene with DorkTracer::Scene::loadFromXml (the reference's
 tinyxml2 parser, parser.cpp:26-577) and flattens the reference's objects into an
 rtg_scene_desc (integration/dork_adapter.cpp).
 
@@ -19,7 +19,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SCENES = os.path.join(ROOT, "tests", "golden", "scenes")
-DORKRT = os.path.join(ROOT, "integration", "_build", "dorkrt")
+DORKRT = os.path.join(ROOT, "oracle", "_ref", "dorkrt")
 FIXTURES = sorted(f[:-4] for f in os.listdir(SCENES) if f.endswith(".xml"))
 
 needs_dorkrt = pytest.mark.skipif(not os.path.exists(DORKRT), reason="dorkrt not built (needs /root/reference)")

@@ -15,7 +15,7 @@ for setting in "$@"; do
   if [ "$setting" = base ]; then envs=(); else envs=("$setting"); fi
   for c in headline c3 c3ton c4; do
     steps=20; [ $c != headline ] && steps=5
-    env "${envs[@]}" timeout -k 10 300 python bench.py --config $c --steps $steps --warmup 2 --no-cpu-baseline --no-sweep --no-extras > $out/bench_${name}_$c.log 2>&1
+    env "${envs[@]}" timeout -k 10 300 python bench.py --full --config $c --steps $steps --warmup 2 --no-cpu-baseline --no-sweep --no-extras > $out/bench_${name}_$c.log 2>&1
     rc=$?; echo "bench $setting $c rc=$rc" >> $st
     [ $rc -ne 0 ] && exit $rc
   done

@@ -15,7 +15,7 @@ for rep in 1 2; do
     if [ $l = base ]; then unset RTGPU_LIB; else export RTGPU_LIB=$PWD/advanced-cpu-raytracing_amd/$l; fi
     for c in ${CONFIGS:-headline}; do
       steps=40; [ $c != headline ] && steps=10
-      timeout -k 10 200 python bench.py --config $c --steps $steps --warmup 3 --no-cpu-baseline --no-sweep --no-extras > $out/bench_${l}_${c}_$rep.log 2>&1
+      timeout -k 10 200 python bench.py --full --config $c --steps $steps --warmup 3 --no-cpu-baseline --no-sweep --no-extras > $out/bench_${l}_${c}_$rep.log 2>&1
       rc=$?; echo "bench $l $c $rep rc=$rc" >> $st
       [ $rc -ne 0 ] && exit $rc
     done

@@ -11,7 +11,7 @@ mkdir -p $out
 for c in $cfgs; do
   for l in "$@"; do
     if [ $l = base ]; then unset RTGPU_LIB; else export RTGPU_LIB=$PWD/advanced-cpu-raytracing_amd/$l; fi
-    timeout -k 10 300 python bench.py --config $c --steps 5 --warmup 2 --no-cpu-baseline > $out/bench_${c}_$l.log 2>&1
+    timeout -k 10 300 python bench.py --full --config $c --steps 5 --warmup 2 --no-cpu-baseline > $out/bench_${c}_$l.log 2>&1
     rc=$?; echo "bench $c $l rc=$rc" >> $out/status.txt
     [ $rc -ne 0 ] && exit $rc
   done

@@ -10,8 +10,8 @@ for rep in 1 2; do
     echo "$(date +%T) start $v.$rep" >> $out/status.txt
     case $v in
       r5) (cd ab_r5 && timeout -k 10 300 python bench.py $args) > $out/$v.$rep.log 2>&1 ;;
-      cur) timeout -k 10 300 python bench.py $args > $out/$v.$rep.log 2>&1 ;;
-      cur_noq) RTG_QNODES=0 timeout -k 10 300 python bench.py $args > $out/$v.$rep.log 2>&1 ;;
+      cur) timeout -k 10 300 python bench.py --full $args > $out/$v.$rep.log 2>&1 ;;
+      cur_noq) RTG_QNODES=0 timeout -k 10 300 python bench.py --full $args > $out/$v.$rep.log 2>&1 ;;
     esac
     rc=$?; echo "$(date +%T) $v.$rep rc=$rc" >> $out/status.txt
     if [ $rc -ne 0 ]; then exit $rc; fi

@@ -19,7 +19,7 @@ for rep in 1 2; do
     [ "$setting" != base ] && IFS=, read -ra envs <<< "$setting"
     for c in ${CONFIGS:-headline}; do
       steps=40; [ $c != headline ] && steps=10
-      timeout -k 10 200 env "${envs[@]}" python bench.py --config $c --steps $steps --warmup 3 --no-cpu-baseline --no-sweep --no-extras > $out/bench_${name}_${c}_$rep.log 2>&1
+      timeout -k 10 200 env "${envs[@]}" python bench.py --full --config $c --steps $steps --warmup 3 --no-cpu-baseline --no-sweep --no-extras > $out/bench_${name}_${c}_$rep.log 2>&1
       rc=$?; echo "bench $name $c $rep rc=$rc" >> $st
       [ $rc -ne 0 ] && exit $rc
     done

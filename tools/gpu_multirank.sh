@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 out=gpurun_out/${1:-mr}
 mkdir -p $out
 for n in 2 4; do
-  RTG_BENCH_BACKEND=gloo timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port $((29500+n)) bench.py --gpus $n --steps 10 --warmup 2 > $out/bench_n$n.log 2>&1
+  RTG_BENCH_BACKEND=gloo timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port $((29500+n)) bench.py --full --gpus $n --steps 10 --warmup 2 > $out/bench_n$n.log 2>&1
   rc=$?; echo "n=$n rc=$rc" >> $out/status.txt
   [ $rc -ne 0 ] && exit $rc
 done

@@ -21,12 +21,12 @@ if [ $skip -eq 0 ]; then
   rc=$?; echo "smoke rc=$rc" >> $st
   if [ $rc -ne 0 ]; then exit $rc; fi
 fi
-timeout -k 10 600 python bench.py $extra > $out/bench.log 2>&1
+timeout -k 10 600 python bench.py --full $extra > $out/bench.log 2>&1
 rc=$?; echo "bench rc=$rc" >> $st
 if [ $rc -ne 0 ]; then exit $rc; fi
 # kernel trace of serial frames (--inflight 1): its per-kernel averages are the live event
 # timings' (with frames in flight, overlapping kernels stretch each other's durations)
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -o run -- python bench.py --steps 20 --warmup 3 --inflight 1 --no-cpu-baseline --no-sweep --no-extras $extra > $out/prof.log 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -o run -- python bench.py --full --steps 20 --warmup 3 --inflight 1 --no-cpu-baseline --no-sweep --no-extras $extra > $out/prof.log 2>&1
 rc=$?; echo "prof rc=$rc" >> $st
 if [ $rc -ne 0 ]; then exit $rc; fi
 timeout -k 10 60 rocprofv3 -L > $out/counters.txt 2>&1
@@ -39,7 +39,7 @@ for pass in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY
             "FETCH_SIZE" \
             "TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCC_READ_REQ_sum TCP_TCC_WRITE_REQ_sum TCP_PENDING_STALL_CYCLES_sum"; do
   k=$((k+1))
-  timeout -s KILL 90 rocprofv3 --pmc $pass --kernel-include-regex "rtg::k_" -f csv -d $out/pmc$k -o run -- python bench.py $args > $out/pmc$k.log 2>&1
+  timeout -s KILL 90 rocprofv3 --pmc $pass --kernel-include-regex "rtg::k_" -f csv -d $out/pmc$k -o run -- python bench.py --full $args > $out/pmc$k.log 2>&1
   rc=$?; echo "pmc$k ($pass) rc=$rc" >> $st
   if [ $rc -ne 0 ]; then exit $rc; fi
 done

@@ -33,9 +33,9 @@ for s in "${steps[@]}"; do
     slivers)
       run slivers 600 python -u tools/diag_slivers.py $out/slivers.json ;;
     bench)
-      run bench 600 python bench.py $extra ;;
+      run bench 600 python bench.py --full $extra ;;
     prof)
-      run prof 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -o run -- python bench.py --steps 20 --warmup 3 --inflight 1 --no-cpu-baseline --no-sweep --no-extras $extra ;;
+      run prof 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -o run -- python bench.py --full --steps 20 --warmup 3 --inflight 1 --no-cpu-baseline --no-sweep --no-extras $extra ;;
     pmc|pmc:*)
       # counter passes (one rocprofv3 --pmc run per group) + one kernel-trace pass of the same
       # bench invocation; pmc:<name> puts them under $out/pmc_<name>/ (tools/pmc_kernels.py)
@@ -55,12 +55,12 @@ for s in "${steps[@]}"; do
                   "TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCC_READ_REQ_sum TCP_TCC_WRITE_REQ_sum TCP_PENDING_STALL_CYCLES_sum"; do
         k=$((k+1))
         echo "$(date +%T) start pmc$name/$k" >> $st
-        timeout -s KILL ${PMC_TIMEOUT:-120} rocprofv3 --pmc $pass --kernel-include-regex "rtg::k_" -f csv -d $pd/pmc$k -o run -- python bench.py $args > $pd/pmc$k.log 2>&1
+        timeout -s KILL ${PMC_TIMEOUT:-120} rocprofv3 --pmc $pass --kernel-include-regex "rtg::k_" -f csv -d $pd/pmc$k -o run -- python bench.py --full $args > $pd/pmc$k.log 2>&1
         rc=$?; echo "$(date +%T) pmc$name/$k ($pass) rc=$rc" >> $st
         if [ $rc -ne 0 ]; then exit $rc; fi
       done
       echo "$(date +%T) start kt$name" >> $st
-      timeout -k 10 ${PMC_TIMEOUT:-120} rocprofv3 --kernel-trace --stats -f csv -d $pd/kt -o run -- python bench.py $args > $pd/kt.log 2>&1
+      timeout -k 10 ${PMC_TIMEOUT:-120} rocprofv3 --kernel-trace --stats -f csv -d $pd/kt -o run -- python bench.py --full $args > $pd/kt.log 2>&1
       rc=$?; echo "$(date +%T) kt$name rc=$rc" >> $st
       if [ $rc -ne 0 ]; then exit $rc; fi
       # summarise on the box and drop the per-dispatch CSVs (gpurun copies back at most 64 MiB)
@@ -73,14 +73,14 @@ for s in "${steps[@]}"; do
       if [ $rc -ne 0 ]; then exit $rc; fi ;;
     configs)
       for c in c2 c3 c3ton c4; do
-        run cfg_$c 300 python bench.py --config $c --no-cpu-baseline $extra
+        run cfg_$c 300 python bench.py --full --config $c --no-cpu-baseline $extra
       done
-      run cfg_c5 400 python bench.py --config c5 --steps 5 --warmup 1 --no-cpu-baseline $extra ;;
+      run cfg_c5 400 python bench.py --full --config c5 --steps 5 --warmup 1 --no-cpu-baseline $extra ;;
     ab)
       run ab 1500 bash tools/gpu_ab_head.sh $tag/ab $AB_LIBS ;;
     multirank)
       # the driver's N-rank launch rehearsed on one GPU (gloo; ranks share GPU 0)
-      run multirank_n2 400 env RTG_BENCH_BACKEND=gloo python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29512 bench.py --gpus 2 --steps 20 --warmup 2 ;;
+      run multirank_n2 400 env RTG_BENCH_BACKEND=gloo python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29512 bench.py --full --gpus 2 --steps 20 --warmup 2 ;;
     envbench)
       # the headline bench (with gather / host-frame / parts / ordered extras) once per setting in
       # $ENV_AB ("base" or NAME=VALUE[,NAME=VALUE])
@@ -88,7 +88,7 @@ for s in "${steps[@]}"; do
         name=$(echo "$setting" | tr "=,/" "___")
         envs=()
         [ "$setting" != base ] && IFS=, read -ra envs <<< "$setting"
-        run envbench_$name 300 env "${envs[@]}" python bench.py --no-sweep --no-cpu-baseline $extra
+        run envbench_$name 300 env "${envs[@]}" python bench.py --full --no-sweep --no-cpu-baseline $extra
       done ;;
     envcfg:*)
       # bench.py --config <c> (no extras) once per setting in $ENV_AB, twice interleaved
@@ -98,7 +98,7 @@ for s in "${steps[@]}"; do
           name=$(echo "$setting" | tr "=,/" "___")
           envs=()
           [ "$setting" != base ] && IFS=, read -ra envs <<< "$setting"
-          run envcfg_${c}_${name}_$rep 400 env "${envs[@]}" python bench.py --config $c --no-extras --no-cpu-baseline --steps ${CFG_STEPS:-10} $extra
+          run envcfg_${c}_${name}_$rep 400 env "${envs[@]}" python bench.py --full --config $c --no-extras --no-cpu-baseline --steps ${CFG_STEPS:-10} $extra
         done
       done ;;
     envpy:*)

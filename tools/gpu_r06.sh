@@ -37,13 +37,13 @@ for s in "${steps[@]}"; do
     slivers)
       run slivers 600 python -u tools/diag_slivers.py $out/slivers.json ;;
     bench)
-      run bench 600 python bench.py $extra ;;
+      run bench 600 python bench.py --full $extra ;;
     prof)
-      run prof 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -o run -- python bench.py --steps 20 --warmup 3 --inflight 1 --no-cpu-baseline --no-sweep --no-extras $extra ;;
+      run prof 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -o run -- python bench.py --full --steps 20 --warmup 3 --inflight 1 --no-cpu-baseline --no-sweep --no-extras $extra ;;
     trace:*)
       # kernel trace of a configuration's bench run with its frame parts, grouped by grid size
       c=${s#trace:}
-      run trace_$c 600 rocprofv3 --kernel-trace --output-format csv -d $out/trace_$c -o run -- python bench.py --config $c --steps 20 --warmup 2 --no-cpu-baseline $extra
+      run trace_$c 600 rocprofv3 --kernel-trace --output-format csv -d $out/trace_$c -o run -- python bench.py --full --config $c --steps 20 --warmup 2 --no-cpu-baseline $extra
       run groups_$c 120 python tools/trace_groups.py $out/trace_$c/run_kernel_trace.csv $out/trace_$c/groups.txt
       find $out/trace_$c -name "*kernel_trace.csv" -delete ;;
     ptrace:*)
@@ -72,12 +72,12 @@ for s in "${steps[@]}"; do
                   "TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCC_READ_REQ_sum TCP_TCC_WRITE_REQ_sum TCP_PENDING_STALL_CYCLES_sum"; do
         k=$((k+1))
         echo "$(date +%T) start pmc$name/$k" >> $st
-        timeout -s KILL ${PMC_TIMEOUT:-120} rocprofv3 --pmc $pass --kernel-include-regex "rtg::k_" -f csv -d $pd/pmc$k -o run -- python bench.py $args > $pd/pmc$k.log 2>&1
+        timeout -s KILL ${PMC_TIMEOUT:-120} rocprofv3 --pmc $pass --kernel-include-regex "rtg::k_" -f csv -d $pd/pmc$k -o run -- python bench.py --full $args > $pd/pmc$k.log 2>&1
         rc=$?; echo "$(date +%T) pmc$name/$k ($pass) rc=$rc" >> $st
         if [ $rc -ne 0 ]; then exit $rc; fi
       done
       echo "$(date +%T) start kt$name" >> $st
-      timeout -k 10 ${PMC_TIMEOUT:-120} rocprofv3 --kernel-trace --stats -f csv -d $pd/kt -o run -- python bench.py $args > $pd/kt.log 2>&1
+      timeout -k 10 ${PMC_TIMEOUT:-120} rocprofv3 --kernel-trace --stats -f csv -d $pd/kt -o run -- python bench.py --full $args > $pd/kt.log 2>&1
       rc=$?; echo "$(date +%T) kt$name rc=$rc" >> $st
       if [ $rc -ne 0 ]; then exit $rc; fi
       # summarise on the box and drop the per-dispatch CSVs (gpurun copies back at most 64 MiB)
@@ -93,16 +93,16 @@ for s in "${steps[@]}"; do
       cpu="--no-cpu-baseline"; [ -n "$CFG_CPU" ] && cpu=""
       for c in ${CFGS:-c2 c3 c3ton c4 c5}; do
         if [ $c == c5 ]; then
-          run cfg_c5 600 python bench.py --config c5 --steps 5 --warmup 1 $cpu $extra
+          run cfg_c5 600 python bench.py --full --config c5 --steps 5 --warmup 1 $cpu $extra
         else
-          run cfg_$c 400 python bench.py --config $c $cpu $extra
+          run cfg_$c 400 python bench.py --full --config $c $cpu $extra
         fi
       done ;;
     inflight:*)
       # one configuration at several frames in flight ($INFLIGHT, default 1 2 4)
       c=${s#inflight:}
       for f in ${INFLIGHT:-1 2 4}; do
-        run inflight_${c}_$f 600 python bench.py --config $c --inflight $f --steps ${CFG_STEPS:-4} --warmup 1 --no-extras --no-cpu-baseline --no-sweep $extra
+        run inflight_${c}_$f 600 python bench.py --full --config $c --inflight $f --steps ${CFG_STEPS:-4} --warmup 1 --no-extras --no-cpu-baseline --no-sweep $extra
       done ;;
     abparts)
       # library A/B ($AB_LIBS, "base" = librtgpu.so) on one configuration ($ABCFG, default c3) with
@@ -110,7 +110,7 @@ for s in "${steps[@]}"; do
       for rep in 1 2; do
         for l in $AB_LIBS; do
           lib=""; [ $l != base ] && lib=$PWD/advanced-cpu-raytracing_amd/$l
-          run abparts_${l}_$rep 400 env RTGPU_LIB=$lib python bench.py --config ${ABCFG:-c3} --no-cpu-baseline --no-sweep --steps 10 $extra
+          run abparts_${l}_$rep 400 env RTGPU_LIB=$lib python bench.py --full --config ${ABCFG:-c3} --no-cpu-baseline --no-sweep --steps 10 $extra
         done
       done
       for l in $AB_LIBS; do
@@ -121,7 +121,7 @@ for s in "${steps[@]}"; do
       run ab 1500 bash tools/gpu_ab_head.sh $tag/ab $AB_LIBS ;;
     multirank)
       # the driver's N-rank launch rehearsed on one GPU (gloo; ranks share GPU 0)
-      run multirank_n2 400 env RTG_BENCH_BACKEND=gloo python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29512 bench.py --gpus 2 --steps 20 --warmup 2 ;;
+      run multirank_n2 400 env RTG_BENCH_BACKEND=gloo python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29512 bench.py --full --gpus 2 --steps 20 --warmup 2 ;;
     envbench)
       # the headline bench (with gather / host-frame / parts / ordered extras) once per setting in
       # $ENV_AB ("base" or NAME=VALUE[,NAME=VALUE])
@@ -129,7 +129,7 @@ for s in "${steps[@]}"; do
         name=$(echo "$setting" | tr "=,/" "___")
         envs=()
         [ "$setting" != base ] && IFS=, read -ra envs <<< "$setting"
-        run envbench_$name 300 env "${envs[@]}" python bench.py --no-sweep --no-cpu-baseline $extra
+        run envbench_$name 300 env "${envs[@]}" python bench.py --full --no-sweep --no-cpu-baseline $extra
       done ;;
     envcfg:*)
       # bench.py --config <c> (no extras) once per setting in $ENV_AB, twice interleaved
@@ -139,7 +139,7 @@ for s in "${steps[@]}"; do
           name=$(echo "$setting" | tr "=,/" "___")
           envs=()
           [ "$setting" != base ] && IFS=, read -ra envs <<< "$setting"
-          run envcfg_${c}_${name}_$rep 400 env "${envs[@]}" python bench.py --config $c --no-extras --no-cpu-baseline --steps ${CFG_STEPS:-10} $extra
+          run envcfg_${c}_${name}_$rep 400 env "${envs[@]}" python bench.py --full --config $c --no-extras --no-cpu-baseline --steps ${CFG_STEPS:-10} $extra
         done
       done ;;
     envpy:*)
