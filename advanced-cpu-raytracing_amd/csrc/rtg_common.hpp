@@ -255,14 +255,46 @@ DEV float vmin3(float a, float b, float c) {
 // this node).  When sure, the three decisions are clear of their boundaries, so each is the
 // sign of one exactly-signed quantity -- tmax, tmax - tmin (nonzero: |.| > slack) and minT - tmin
 // (a rounded difference has the sign of the exact one) -- and the conjunction is min(...) > 0;
-// `sure` is min(|tmax - tmin| - slack, |tmin - minT| - slack', |tmax| - 1e-30) > 0 (each a rounded
+// `sure` is min(|tmax - tmin| - slack, |tmin - minT| - slack', |tmax| - slack0) > 0 (each a rounded
 // difference: exact sign; the last a hair stricter than >=), slack0 = inf when the ray's
 // reciprocals are not exact enough (q.fast).  A NaN term leaves the lane unsure; a sure lane has
 // no NaN among tmax, d1, d2.  Unsure lanes inside their walk take the exact test (uniform branch).
 // Returns a value whose sign is the answer (> 0: the lane takes part and the box passes), so a
 // caller's ballot of `> 0` is one comparison; actf > 0: the lane takes part.
 // INT: actf is an integer (rel), so `act & !sure` is one comparison, !(max(su, 0.5 - actf) > 0).
-// box_pass_t takes the six slab distances (m - o) * rcp; the box for the exact fallback.
+// box_pass_t takes the six slab distances; the box for the exact fallback.
+//
+// The packet walks' slab distances are fused (SlabFma): t = fma(m, inv, n) with n = -fl(o * inv)
+// computed once per (instance-local) ray, one instruction per box plane with the box coordinate
+// as the scalar operand, where (m - o) * inv takes two.  Against the reference's fl(fl(m - o) / d):
+// inv = (1 / d)(1 + e1), |e1| <= 2^-23 (v_rcp_f32, 1 ulp); n = -(o inv)(1 + e2), |e2| <= 2^-24; the
+// fma rounds once, (1 + e3).  So t = ((m - o) / d (1 + e1) - o inv e2)(1 + e3): within
+// (2^-23 + 2^-24) |t| + 2^-24 |o inv| (1 + 2^-24) of the true quotient, and the reference's two
+// roundings are within 2^-23 |t| of it -- together at most
+//     1.25 * 2^-22 |t| + 2^-24 A (1 + 2^-22),    A = max_k |fl(o_k inv_k)|.
+// The absolute term is new: the subtract-first form cancels exactly and its error is purely
+// relative.  The exact decisions keep their 2^-20 relative slack (more than 3x the relative bound
+// per distance) and take the absolute term into the per-lane constant
+//     slack0 = fast ? 1e-30 + 2^-21 A : inf
+// (4x the absolute bound for tmin < minT and |tmax| > 0, 2x for the two distances of tmax - tmin),
+// which is also the third certainty term, |tmax| - slack0: a literal became a register operand, so
+// the node loop gains no instruction.  Unsure lanes take box_hit as before: every decision, node
+// visit and triangle test is what it was.  (tests/test_slab_bound_model.py models both predicates.)
+struct SlabFma {
+    float ix, iy, iz;                 // rcp(d)
+    float nx, ny, nz;                 // -fl(o * rcp(d))
+    float A;                          // max |fl(o * rcp(d))|
+};
+DEV SlabFma slab_fma(const Ray& r, const RayRcp& q) {
+    SlabFma s;
+    const float px = r.o.x * q.ix, py = r.o.y * q.iy, pz = r.o.z * q.iz;
+    s.ix = q.ix; s.iy = q.iy; s.iz = q.iz;
+    s.nx = -px; s.ny = -py; s.nz = -pz;
+    s.A = fmaxf(fmaxf(fabsf(px), fabsf(py)), fabsf(pz));
+    return s;
+}
+// the exact decisions' per-lane constant (a ray off the fast path is never sure)
+DEV float slab_slack0(const SlabFma& s, bool fast) { return fast ? fmaf(0x1p-21f, s.A, 1e-30f) : INFINITY; }
 template <bool INT = false>
 DEV float box_pass_t(float tx1, float tx2, float ty1, float ty2, float tz1, float tz2, float mnx, float mny, float mnz,
                      float mxx, float mxy, float mxz, const Ray& r, float minT, float actf, float slack0) {
@@ -273,7 +305,7 @@ DEV float box_pass_t(float tx1, float tx2, float ty1, float ty2, float tz1, floa
     // (NaN-propagating minimum, v_minimum3_f32: any NaN term -- an infinite box face, inf - inf
     // -- leaves the lane unsure)
     const float su = vmin3(fabsf(d1) - fmaf(0x1p-20f, atmin + atmax, slack0), fabsf(d2) - fmaf(0x1p-20f, atmin, slack0),
-                           atmax - 1e-30f);
+                           atmax - slack0);
     float pv = __builtin_elementwise_minimum(fminf(fminf(tmax, d1), d2), actf);   // (a NaN actf: not taking part)
     const bool unsure = INT ? !(fmaxf(su, 0.5f - actf) > 0.0f) : (actf > 0.0f) & !(su > 0.0f);
     if (__builtin_expect(__ballot(unsure) != 0, 0)) {
@@ -282,14 +314,14 @@ DEV float box_pass_t(float tx1, float tx2, float ty1, float ty2, float tz1, floa
     return pv;
 }
 template <bool INT = false>
-DEV float box_pass_v(float mnx, float mny, float mnz, float mxx, float mxy, float mxz, const Ray& r, const RayRcp& q,
+DEV float box_pass_v(float mnx, float mny, float mnz, float mxx, float mxy, float mxz, const Ray& r, const SlabFma& q,
                      float minT, float actf, float slack0) {
-    const float tx1 = (mnx - r.o.x) * q.ix, tx2 = (mxx - r.o.x) * q.ix;
-    const float ty1 = (mny - r.o.y) * q.iy, ty2 = (mxy - r.o.y) * q.iy;
-    const float tz1 = (mnz - r.o.z) * q.iz, tz2 = (mxz - r.o.z) * q.iz;
+    const float tx1 = fmaf(mnx, q.ix, q.nx), tx2 = fmaf(mxx, q.ix, q.nx);
+    const float ty1 = fmaf(mny, q.iy, q.ny), ty2 = fmaf(mxy, q.iy, q.ny);
+    const float tz1 = fmaf(mnz, q.iz, q.nz), tz2 = fmaf(mxz, q.iz, q.nz);
     return box_pass_t<INT>(tx1, tx2, ty1, ty2, tz1, tz2, mnx, mny, mnz, mxx, mxy, mxz, r, minT, actf, slack0);
 }
-DEV bool box_pass_pk(float mnx, float mny, float mnz, float mxx, float mxy, float mxz, const Ray& r, const RayRcp& q,
+DEV bool box_pass_pk(float mnx, float mny, float mnz, float mxx, float mxy, float mxz, const Ray& r, const SlabFma& q,
                      float minT, int rel, float slack0) {
     // rel = i + 1 - resume > 0: the lane's walk reaches the node (as a float: sign exact)
     // (compared after the merge: the caller's ballot of it is then that comparison's mask)
@@ -856,7 +888,8 @@ DEV bool walk_bvh_packet(const DevScene& S, int begin, int end, const Ray& r, fl
     const int face0 = hitFace;
     bool hit = false;
     const RayRcp q = ray_rcp(r);
-    const float slack0 = q.fast ? 1e-30f : INFINITY;   // box_pass_pk: a ray off the fast path is never sure
+    const SlabFma sf = slab_fma(r, q);               // (SC: the fused slab distances of box_pass_pk)
+    const float slack0 = slab_slack0(sf, q.fast);    // box_pass_pk: a ray off the fast path is never sure
     const int kDone = 0x7FFFFFFF;
     int resume = begin;                              // per lane: first node it takes part in again
     int i = begin;                                   // wave-uniform
@@ -897,7 +930,7 @@ DEV bool walk_bvh_packet(const DevScene& S, int begin, int end, const Ray& r, fl
         bool pass;
         if constexpr (SC) {
             if (act) c.template node<ANY>();
-            pass = box_pass_pk(a.x, a.y, a.z, a.w, b.x, b.y, r, q, minT, ip1 - resume, slack0);
+            pass = box_pass_pk(a.x, a.y, a.z, a.w, b.x, b.y, r, sf, minT, ip1 - resume, slack0);
             // a lane inside its walk that fails the box resumes at the box's skip; lanes outside it
             // already wait for a node past this box's subtree (resume >= skip), as do lanes that pass
             resume = max(resume, pass ? 0 : skip);
@@ -1200,21 +1233,51 @@ struct AnyDefer {
 #ifndef RTG_PK_MAX_STEPS
 #define RTG_PK_MAX_STEPS 4096
 #endif
-// slab_cons as a value (> 0: the conservative test passes and the lane walks, livef > 0): tmax >
-// -1e-30 is tmax + 1e-30 > 0 and tmin < minTc is minTc - tmin > 0 (exact: rounded sums and
-// differences keep their signs); tmax >= tmin (1 - 2^-21) - 1e-30 is loosened by another 1e-30
-// so that it becomes a strict comparison too -- the test only has to keep every box the exact
-// test keeps (walk_wide_any_pk: extra boxes change no answer).
-DEV float slab_cons_v(float lx, float ly, float lz, float hx, float hy, float hz, const SlabRay& s, float minTc,
+// slab_cons as a value (> 0: the conservative test passes and the lane walks, livef > 0), on fused
+// slab distances (SlabFma above) whose absolute error term is folded into the per-ray constants,
+// axis by axis.  A ray-wide slack of 2^-22 max_k |o_k inv_k| in the three comparisons would keep
+// boxes for nothing whenever one direction component is small: that axis's |o inv| is huge and
+// would swamp the -eps / d of a ray leaving a flat box on another axis (`spheres`: 692 face tests
+// where the reference's walk has none).  Instead each axis carries two constants,
+//     a_k = n_k - s_k e_k  (with the box minimum),   b_k = n_k + s_k e_k  (with the maximum),
+//     n_k = -fl(o_k inv_k),  e_k = 2^-22 |n_k|,  s_k = sign(inv_k),
+// so the axis's entry distance -- fma(lo, inv, a) for inv > 0, fma(hi, inv, b) for inv < 0 -- is
+// lowered by e_k and its exit distance raised by e_k: four times the fused form's absolute error
+// 2^-24 |n_k| (1 + 2^-22), less the 2^-24 |n_k| of rounding a_k / b_k themselves.  min / max pick
+// entry and exit as before (entry - e <= exit + e).  What is left is relative, 1.25 * 2^-22 |t| per
+// distance: exact tmax > 0, tmax >= tmin, tmin < minT imply tmax + 1e-30 > 0,
+// tmax - (tmin (1 - 2^-20) - 1e-30) + 1e-30 > 0 (two distances carry 2.5 * 2^-22 together: 2^-20
+// covers it with margin, 2^-21 would not) and minTc - tmin > 0 with minTc = minT (1 + 2^-20); the
+// 1e-30 terms cover subnormal products.  Rounded sums and differences keep their signs, so each
+// is one strict comparison.  The test only has to keep every box the exact test keeps
+// (walk_wide_any_pk: extra boxes change no answer).  Six constants per ray instead of three
+// origin components; no instruction in the loop beyond the six fused distances.
+struct SlabCons {
+    float ix, iy, iz;
+    float ax, ay, az, bx, by, bz;
+    bool ok;                          // |o inv| finite (else the ray takes the reference walk)
+};
+DEV SlabCons slab_cons_ray(const Ray& r, const RayRcp& q) {
+    SlabCons s;
+    const float px = r.o.x * q.ix, py = r.o.y * q.iy, pz = r.o.z * q.iz;
+    const float ex = copysignf(0x1p-22f * fabsf(px), q.ix), ey = copysignf(0x1p-22f * fabsf(py), q.iy),
+                ez = copysignf(0x1p-22f * fabsf(pz), q.iz);
+    s.ix = q.ix; s.iy = q.iy; s.iz = q.iz;
+    s.ax = -px - ex; s.ay = -py - ey; s.az = -pz - ez;
+    s.bx = -px + ex; s.by = -py + ey; s.bz = -pz + ez;
+    s.ok = fmaxf(fmaxf(fabsf(px), fabsf(py)), fabsf(pz)) <= 0x1p100f;
+    return s;
+}
+DEV float slab_cons_v(float lx, float ly, float lz, float hx, float hy, float hz, const SlabCons& s, float minTc,
                       float& tnear, float livef) {
-    const float tx1 = (lx - s.o.x) * s.ix, tx2 = (hx - s.o.x) * s.ix;
-    const float ty1 = (ly - s.o.y) * s.iy, ty2 = (hy - s.o.y) * s.iy;
-    const float tz1 = (lz - s.o.z) * s.iz, tz2 = (hz - s.o.z) * s.iz;
+    const float tx1 = fmaf(lx, s.ix, s.ax), tx2 = fmaf(hx, s.ix, s.bx);
+    const float ty1 = fmaf(ly, s.iy, s.ay), ty2 = fmaf(hy, s.iy, s.by);
+    const float tz1 = fmaf(lz, s.iz, s.az), tz2 = fmaf(hz, s.iz, s.bz);
     const float tmin = fmaxf(fmaxf(fminf(tx1, tx2), fminf(ty1, ty2)), fminf(tz1, tz2));
     const float tmax = fminf(fminf(fmaxf(tx1, tx2), fmaxf(ty1, ty2)), fmaxf(tz1, tz2));
     tnear = tmin;
     return __builtin_elementwise_minimum(
-        vmin3(tmax + 1e-30f, (tmax - fmaf(tmin, 1.0f - 0x1p-21f, -1e-30f)) + 1e-30f, minTc - tmin), livef);
+        vmin3(tmax + 1e-30f, (tmax - fmaf(tmin, 1.0f - 0x1p-20f, -1e-30f)) + 1e-30f, minTc - tmin), livef);
 }
 
 template <bool STATS, bool DEFER = false>
@@ -1222,15 +1285,14 @@ DEV int walk_wide_any_pk(const DevScene& S, int node, const Ray& lr, float minT0
                          Cnt<STATS>& c, AnyDefer* ad = nullptr) {
     // The lane state as values, every wave-level test one comparison (the mask version kept
     // live / occluded / undecided and the four child masks as SGPR pairs merged at every block
-    // and spilled to VGPR lanes): livef > 0 walking, occ / und flags, a child's hk > 0 taking it.
+    // and spilled to VGPR lanes): livef > 0 walking (-2: occluded), the und flag, a child's hk > 0 taking it.
     const RayRcp q = ray_rcp(lr);
-    const float minTc = minT0 * (1.0f + 0x1p-21f);
-    const SlabRay sr = slab_ray(lr, q);
-    const float slack0 = q.fast ? 1e-30f : INFINITY;
+    const SlabCons sr = slab_cons_ray(lr, q);
+    const bool fast = q.fast & sr.ok;
+    const float minTc = minT0 * (1.0f + 0x1p-20f);
     const float icf = inst_conf ? 1.0f : -1.0f;
-    float livef = q.fast ? 1.0f : -1.0f;
-    int occ = 0;
-    int und = q.fast ? 0 : 1;                        // zero / tiny direction component: reference walk
+    float livef = fast ? 1.0f : -1.0f;
+    int und = fast ? 0 : 1;                          // zero / tiny direction component: reference walk
     __shared__ int pk_stack[4][RTG_PK_STACK];        // the wave's stack (256-thread blocks)
     int* const stk = pk_stack[(threadIdx.x >> 6) & 3];
     int sp = 0;                                      // wave-uniform
@@ -1310,15 +1372,22 @@ DEV int walk_wide_any_pk(const DevScene& S, int node, const Ray& lr, float minT0
                 // (necessary), and at limit (sufficient, for an instance whose world box passes)
                 rtg_s8 rn;
                 sload_node(rec_at<32>(S.nodes, ra[3]), rn);
+                // (few faces get here: the exact decisions' constants are made on the spot, from a
+                // laundered origin so that they are not hoisted into the walk's registers -- hoisted,
+                // k_frame's scratch is 28 B per lane against 8; a lane with okv > 0 walks, so it is
+                // on the fast path)
+                Ray er = lr;
+                asm volatile("" : "+v"(er.o.x), "+v"(er.o.y), "+v"(er.o.z));
+                const SlabFma sf = slab_fma(er, q);
+                const float slack0 = slab_slack0(sf, true);
                 const float rv = box_pass_v(__int_as_float(rn[0]), __int_as_float(rn[1]), __int_as_float(rn[2]),
-                                            __int_as_float(rn[3]), __int_as_float(rn[4]), __int_as_float(rn[5]), lr, q,
+                                            __int_as_float(rn[3]), __int_as_float(rn[4]), __int_as_float(rn[5]), er, sf,
                                             minT0, okv, slack0);
                 const float sv = box_pass_v(__int_as_float(rn[0]), __int_as_float(rn[1]), __int_as_float(rn[2]),
-                                            __int_as_float(rn[3]), __int_as_float(rn[4]), __int_as_float(rn[5]), lr, q,
+                                            __int_as_float(rn[3]), __int_as_float(rn[4]), __int_as_float(rn[5]), er, sf,
                                             limit, __builtin_elementwise_minimum(rv, icf), slack0);
                 const bool suff = sv > 0.0f;
-                occ = suff ? 1 : occ;
-                livef = suff ? -1.0f : livef;
+                livef = suff ? -2.0f : livef;         // (-2: occluded)
                 hk = suff ? -1.0f : hk;
                 und |= (rv > 0.0f) & !suff;
             }
@@ -1331,7 +1400,7 @@ DEV int walk_wide_any_pk(const DevScene& S, int node, const Ray& lr, float minT0
         if (sp == 0) break;
         node = stk[--sp];
     }
-    return occ ? 1 : (und ? -1 : 0);
+    return livef < -1.5f ? 1 : (und ? -1 : 0);
 }
 
 // CastShadowRay on the wide BVH: objects in any order (the answer is a boolean), spheres

@@ -385,9 +385,15 @@ __global__ __launch_bounds__(256, MODE >= SH_FUSED ? (FAST ? RTG_WIDE_WAVES(FEAT
                                                                                    const PassOut O,
                                                                                    DevCounters* counters) {
     constexpr bool ONE = MODE != SH_GENERAL;
+    // the block's queue segment (SH_GENERAL / SH_ONE).  The fused layouts append nothing and
+    // nothing reads their q_count (its readers are k_shadow*, which those layouts never launch), so
+    // they have no counter, no barriers and no store: their waves end independently.
+    constexpr bool QUEUE = MODE < SH_FUSED;
     __shared__ int seg_count;
-    if (threadIdx.x == 0) seg_count = 0;
-    __syncthreads();
+    if constexpr (QUEUE) {
+        if (threadIdx.x == 0) seg_count = 0;
+        __syncthreads();
+    }
     int px, py, crow, slab;
     tile_pixel(P, px, py, crow, slab);
     const int sample = sample0 + slab;
@@ -679,8 +685,10 @@ __global__ __launch_bounds__(256, MODE >= SH_FUSED ? (FAST ? RTG_WIDE_WAVES(FEAT
         }
     }
     }
-    __syncthreads();
-    if (threadIdx.x == 0) W.q_count[blockIdx.x] = seg_count;
+    if constexpr (QUEUE) {
+        __syncthreads();
+        if (threadIdx.x == 0) W.q_count[blockIdx.x] = seg_count;
+    }
     flush_counters<STATS>(cn, counters);
 }
 
