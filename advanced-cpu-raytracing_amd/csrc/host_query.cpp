@@ -1,0 +1,258 @@
+// rtg_desc_trace_rays: the reference's ray queries restated on the host over a scene
+// description, with no device -- the yardstick the device queries (rtg_query.hip) are tested
+// against bit for bit.  A plain restatement: true divisions, recursive BVH descent, sequential
+// leaf loops, every float operation in the reference's order (this file is compiled with
+// -ffp-contract=off like the rest of the host code).
+//
+//   IntersectObjects / CastShadowRay   raytracer.cpp:625-643, :585-623
+//   BVH::IntersectBVH                  bvh.cpp:5-30
+//   Mesh::Intersect / IntersectFace    mesh.cpp:158-240
+//   Sphere::Intersect                  sphere.cpp:13-70
+//   InstancedMesh::Intersect           instancedMesh.cpp:16-66
+//   BoundingBox::doesIntersectWith     shape.hpp:78-100
+#include "host_query.hpp"
+
+#include <algorithm>
+#include <cmath>
+#include <thread>
+#include <vector>
+
+#include "host_math.hpp"
+
+namespace rtg {
+namespace {
+
+struct HRay {
+    V3 o, d;
+};
+
+// matrix.hpp:56-81 on a row-major double[16]: double accumulation, narrowed to float
+V3 xform(const double* m, const V3& v, float w) {
+    return V3((float)(m[0] * v.x + m[1] * v.y + m[2] * v.z + m[3] * w),
+              (float)(m[4] * v.x + m[5] * v.y + m[6] * v.z + m[7] * w),
+              (float)(m[8] * v.x + m[9] * v.y + m[10] * v.z + m[11] * w));
+}
+
+// BoundingBox::doesIntersectWith: the x slab by comparison, y / z by fmin / fmax
+bool box_hit(const float* mn, const float* mx, const HRay& r, float minT) {
+    float tx1 = (mn[0] - r.o.x) / r.d.x;
+    float tx2 = (mx[0] - r.o.x) / r.d.x;
+    float tmin = tx1, tmax = tx2;
+    if (tx1 > tx2) { tmin = tx2; tmax = tx1; }
+    float ty1 = (mn[1] - r.o.y) / r.d.y;
+    float ty2 = (mx[1] - r.o.y) / r.d.y;
+    tmin = std::fmax(tmin, std::fmin(ty1, ty2));
+    tmax = std::fmin(tmax, std::fmax(ty1, ty2));
+    float tz1 = (mn[2] - r.o.z) / r.d.z;
+    float tz2 = (mx[2] - r.o.z) / r.d.z;
+    tmin = std::fmax(tmin, std::fmin(tz1, tz2));
+    tmax = std::fmin(tmax, std::fmax(tz1, tz2));
+    return tmax > 0 && tmax >= tmin && tmin < minT;
+}
+
+// determinant (helperMath.cpp:132-138)
+float det3(float m00, float m01, float m02, float m10, float m11, float m12, float m20, float m21, float m22) {
+    float first = m00 * (m11 * m22 - m12 * m21);
+    float second = m10 * (m02 * m21 - m01 * m22);
+    float third = m20 * (m01 * m12 - m11 * m02);
+    return first + second + third;
+}
+
+// Mesh::IntersectFace: Cramer's rule, the early outs in the reference's order
+bool face_hit(const rtg_face& F, const HRay& r, float minT, float& tout) {
+    const float e1x = F.v0.x - F.v1.x, e1y = F.v0.y - F.v1.y, e1z = F.v0.z - F.v1.z;
+    const float e2x = F.v0.x - F.v2.x, e2y = F.v0.y - F.v2.y, e2z = F.v0.z - F.v2.z;
+    const float dx = r.d.x, dy = r.d.y, dz = r.d.z;
+    float detA = det3(e1x, e2x, dx, e1y, e2y, dy, e1z, e2z, dz);
+    if (detA == 0) return false;
+    const float sx = F.v0.x - r.o.x, sy = F.v0.y - r.o.y, sz = F.v0.z - r.o.z;
+    float beta = det3(sx, e2x, dx, sy, e2y, dy, sz, e2z, dz) / detA;
+    if (beta < 0) return false;
+    float gama = det3(e1x, sx, dx, e1y, sy, dy, e1z, sz, dz) / detA;
+    if (gama < 0 || gama + beta > 1) return false;
+    float t = det3(e1x, e2x, sx, e1y, e2y, sy, e1z, e2z, sz) / detA;
+    tout = t;
+    return t > 0.0f && t < minT;
+}
+
+// Sphere::Intersect's root selection and acceptance on the local ray
+bool sphere_hit(const rtg_object& ob, const HRay& lr, float minT, float& tout) {
+    const V3 center = from_f3(ob.center);
+    V3 oc = lr.o - center;
+    float c = dot(oc, oc) - (ob.radius * ob.radius);
+    float b = 2 * dot(lr.d, oc);
+    float a = dot(lr.d, lr.d);
+    float delta = b * b - (4 * a * c);
+    if (delta < 0.0f) return false;
+    delta = sqrtf(delta);
+    a = (float)(2.0 * a);
+    float t1 = (-b + delta) / a;
+    float t2 = (-b - delta) / a;
+    float t = t1 < t2 ? t1 : t2;
+    if (t1 < t2) { t = (t1 > 0.0f) ? t1 : t2; }
+    else if (t2 < t1) { t = (t2 > 0.0f) ? t2 : t1; }
+    tout = t;
+    return t < minT && t > 0.0f;
+}
+
+// the world ray in the object's local space (mesh.cpp:164-170, sphere.cpp:23-29,
+// instancedMesh.cpp:33-39)
+HRay local_ray(const rtg_object& ob, const HRay& r, float time) {
+    HRay lr;
+    lr.o = xform(ob.inv_transform, r.o, 1.0f);
+    lr.d = xform(ob.inv_transform, r.d, 0.0f);
+    if (ob.flags & RTG_OBJF_MOTION_BLUR) lr.o = lr.o + from_f3(ob.motion_blur) * time;
+    return lr;
+}
+
+struct MeshWalk {
+    const rtg_bvh_node* nodes;    // the mesh's nodes
+    const rtg_face* faces;        // the mesh's faces (BVH order)
+    HRay r;                       // local ray
+    float minT;
+    int face = -1;                // mesh-local index of the last accepted face
+    bool any = false;             // stop at the first accepted face
+    bool done = false;
+};
+
+// BVH::IntersectBVH
+bool intersect_bvh(MeshWalk& w, int k) {
+    const rtg_bvh_node& n = w.nodes[k];
+    if (!box_hit(n.bmin, n.bmax, w.r, w.minT)) return false;
+    bool hasHit = false;
+    if (n.left < 0) {
+        for (int i = n.first; i < n.first + n.count; ++i) {
+            float t;
+            if (face_hit(w.faces[i], w.r, w.minT, t)) {
+                w.minT = t;
+                w.face = i;
+                hasHit = true;
+                if (w.any) {
+                    w.done = true;
+                    return true;
+                }
+            }
+        }
+    } else {
+        const bool hitLeft = intersect_bvh(w, n.left);
+        if (w.done) return true;
+        const bool hitRight = intersect_bvh(w, n.left + 1);
+        hasHit = hitLeft || hitRight;
+    }
+    return hasHit;
+}
+
+// One ray through the object loop.  any: CastShadowRay with minT0 = limit = tmax -- every
+// accepted hit has t < limit, so the first one answers; emissive meshes are skipped and the
+// motion-blur time is 0.
+void trace_one(const rtg_scene_desc* d, const rtg_ray& q, bool any, rtg_hit& out, float* normal) {
+    HRay r;
+    r.o = V3(q.ox, q.oy, q.oz);
+    r.d = V3(q.dx, q.dy, q.dz);
+    const float time = any ? 0.0f : q.time;
+    float minT = q.tmax;
+    int obj = -1, face = -1;
+    V3 hitOrigin;                 // the world origin the accepted hit's object saw
+    for (int k = 0; k < d->num_objects; ++k) {
+        const rtg_object& ob = d->objects[k];
+        if (ob.kind == RTG_OBJ_SPHERE) {
+            float t;
+            if (sphere_hit(ob, local_ray(ob, r, time), minT, t)) {
+                minT = t; obj = k; face = -1; hitOrigin = r.o;
+                if (any) break;
+            }
+            continue;
+        }
+        if (any && (ob.flags & RTG_OBJF_SHADOW_SKIP)) continue;
+        const rtg_mesh& M = d->meshes[ob.mesh];
+        if (ob.kind == RTG_OBJ_INSTANCE) {
+            // the world box first, on the blurred origin; a miss leaves the offset on the ray
+            // (instancedMesh.cpp:23-29: the origin is restored only inside the branch)
+            HRay wr = r;
+            if (ob.flags & RTG_OBJF_MOTION_BLUR) wr.o = wr.o + from_f3(ob.motion_blur) * time;
+            if (!box_hit(ob.bbox_min, ob.bbox_max, wr, minT)) {
+                r.o = wr.o;
+                continue;
+            }
+        }
+        MeshWalk w;
+        w.nodes = d->nodes + M.node_offset;
+        w.faces = d->faces + M.face_offset;
+        w.r = local_ray(ob, r, time);
+        w.minT = minT;
+        w.any = any;
+        // Mesh::Intersect tests the mesh's own box before its BVH (mesh.cpp:172)
+        if (ob.kind == RTG_OBJ_MESH && !box_hit(ob.bbox_min, ob.bbox_max, w.r, minT)) continue;
+        if (M.node_count <= 0) continue;
+        if (intersect_bvh(w, 0)) {
+            minT = w.minT; obj = k; face = M.face_offset + w.face; hitOrigin = r.o;
+            if (any) break;
+        }
+    }
+    out.t = minT;
+    out.object = any ? (obj >= 0 ? 0 : -1) : obj;
+    out.face = any ? -1 : face;
+    out.pad = 0;
+    if (!normal || any) return;
+    normal[0] = normal[1] = normal[2] = normal[3] = 0.f;
+    if (obj < 0) return;
+    const rtg_object& ob = d->objects[obj];
+    V3 n;
+    if (face < 0) {               // sphere.cpp:66,84 and the normal's transform
+        HRay hr;
+        hr.o = hitOrigin;
+        hr.d = r.d;
+        const HRay lr = local_ray(ob, hr, time);
+        const V3 lp = lr.o + lr.d * minT;
+        n = makeUnit(lp - from_f3(ob.center));
+    } else {                      // mesh.cpp:241, :362-364, :179 / instancedMesh.cpp:57
+        n = from_f3(d->faces[face].n);
+        if (ob.flags & RTG_OBJF_NORMAL_TWICE) n = makeUnit(xform(ob.base_inv_transpose, n, 0.0f));
+    }
+    n = makeUnit(xform(ob.inv_transpose, n, 0.0f));
+    normal[0] = n.x; normal[1] = n.y; normal[2] = n.z;
+}
+
+}  // namespace
+
+int host_trace_rays(const rtg_scene_desc* d, const rtg_ray* rays, int64_t n, uint32_t flags, rtg_hit* hits,
+                    float* normals, std::string& err) {
+    if (!d) { err = "null description"; return RTG_ERR_INVALID; }
+    if (n < 0 || n > INT32_MAX) { err = "ray count out of range"; return RTG_ERR_INVALID; }
+    if (flags & ~(uint32_t)(RTG_QUERY_ANY_HIT | RTG_QUERY_COHERENT)) { err = "unknown query flags"; return RTG_ERR_INVALID; }
+    if (d->num_faces > 0 && d->num_nodes == 0) {
+        err = "the description has no BVH nodes (RTG_LOAD_DEVICE_BVH): it is for rtg_scene_create only";
+        return RTG_ERR_INVALID;
+    }
+    if (n == 0) return RTG_OK;
+    if (!rays || !hits) { err = "null buffer"; return RTG_ERR_INVALID; }
+    for (int i = 0; i < d->num_objects; ++i) {
+        const rtg_object& o = d->objects[i];
+        if (o.kind != RTG_OBJ_SPHERE && (o.mesh < 0 || o.mesh >= d->num_meshes)) {
+            err = "object with a bad mesh index";
+            return RTG_ERR_INVALID;
+        }
+    }
+    const bool any = (flags & RTG_QUERY_ANY_HIT) != 0;
+    // rays are independent: contiguous chunks over a few threads
+    const int64_t kChunk = 4096;
+    const int nt = (int)std::min<int64_t>(std::min(8u, std::max(1u, std::thread::hardware_concurrency())),
+                                          (n + kChunk - 1) / kChunk);
+    auto work = [&](int64_t b, int64_t e) {
+        for (int64_t i = b; i < e; ++i) trace_one(d, rays[i], any, hits[i], normals ? normals + 4 * i : nullptr);
+    };
+    if (nt <= 1) {
+        work(0, n);
+        return RTG_OK;
+    }
+    std::vector<std::thread> pool;
+    const int64_t per = (n + nt - 1) / nt;
+    for (int t = 0; t < nt; ++t) {
+        const int64_t b = t * per, e = std::min(n, b + per);
+        if (b < e) pool.emplace_back(work, b, e);
+    }
+    for (auto& th : pool) th.join();
+    return RTG_OK;
+}
+
+}  // namespace rtg

@@ -1,0 +1,17 @@
+// Host-only ray queries over a scene description (rtgpu.h rtg_desc_trace_rays).
+#pragma once
+
+#include <cstdint>
+#include <string>
+
+#include "rtgpu.h"
+
+namespace rtg {
+
+// The reference's IntersectObjects / CastShadowRay for n rays over the description's own BVH
+// nodes; normals nullable (4 floats per ray, closest hit only).  Returns an rtg_status; `err`
+// describes a failure.
+int host_trace_rays(const rtg_scene_desc* d, const rtg_ray* rays, int64_t n, uint32_t flags, rtg_hit* hits,
+                    float* normals, std::string& err);
+
+}  // namespace rtg

@@ -13,6 +13,7 @@
 #include <cstdlib>
 
 #include "host_assets.hpp"
+#include "host_query.hpp"
 #include "host_scene.hpp"
 #include "rtg_ahb.hpp"
 #include "rtg_device.hpp"
@@ -145,6 +146,10 @@ struct rtg_scene {
     float* d_hdr = nullptr;
     unsigned char* d_ldr = nullptr;
     size_t d_pixels = 0;
+    // scratch of the host-buffer ray queries (rtg_trace_rays, rtg_camera_rays): rays, hits,
+    // normals; grown on demand, never touched by the device-buffer entry points
+    void* q_mem[3] = {};
+    size_t q_cap[3] = {};
     // block -> tile tables, one per (tiles_x, tiles_y) met (never re-uploaded: kernels of
     // several streams may be reading them)
     std::vector<std::unique_ptr<TileMap>> tile_maps;
@@ -174,6 +179,8 @@ struct rtg_scene {
             if (e) (void)hipEventDestroy(e);
         if (d_hdr) (void)hipFree(d_hdr);
         if (d_ldr) (void)hipFree(d_ldr);
+        for (void* q : q_mem)
+            if (q) (void)hipFree(q);
         for (auto& w : work) {
             if (w.mem) (void)hipFree(w.mem);
             if (w.dq) (void)hipFree(w.dq);
@@ -962,11 +969,8 @@ static int ensure_tile_map(rtg_scene* s, int tx, int ty, const int** out) {
     return RTG_OK;
 }
 
-static int prepare(rtg_scene* s, const rtg_render_opts* o, rtg::DevCamera& C, rtg::RenderParams& P) {
-    if (!s || !o) return set_err(RTG_ERR_INVALID, "null argument");
-    if (o->camera < 0 || o->camera >= (int)s->cameras.size()) return set_err(RTG_ERR_INVALID, "bad camera %d", o->camera);
-    const rtg_camera& c = s->cameras[o->camera];
-    if (c.width <= 0 || c.height <= 0) return set_err(RTG_ERR_INVALID, "camera %d has an empty image", o->camera);
+// A camera's device record (shared by the renders and rtg_camera_rays*).
+static void dev_camera(const rtg_camera& c, rtg::DevCamera& C) {
     std::memset(&C, 0, sizeof(C));
     auto cp = [](float* d, const rtg_float3& v) { d[0] = v.x; d[1] = v.y; d[2] = v.z; };
     cp(C.pos, c.position); cp(C.gaze, c.gaze); cp(C.up, c.up); cp(C.right, c.right); cp(C.q, c.q);
@@ -975,6 +979,14 @@ static int prepare(rtg_scene* s, const rtg_render_opts* o, rtg::DevCamera& C, rt
     C.width = c.width; C.height = c.height; C.spp = c.spp < 1 ? 1 : c.spp;
     C.path_tracing = c.path_tracing; C.next_event = c.next_event;
     C.importance_sampling = c.importance_sampling; C.russian_roulette = c.russian_roulette;
+}
+
+static int prepare(rtg_scene* s, const rtg_render_opts* o, rtg::DevCamera& C, rtg::RenderParams& P) {
+    if (!s || !o) return set_err(RTG_ERR_INVALID, "null argument");
+    if (o->camera < 0 || o->camera >= (int)s->cameras.size()) return set_err(RTG_ERR_INVALID, "bad camera %d", o->camera);
+    const rtg_camera& c = s->cameras[o->camera];
+    if (c.width <= 0 || c.height <= 0) return set_err(RTG_ERR_INVALID, "camera %d has an empty image", o->camera);
+    dev_camera(c, C);
     std::memset(&P, 0, sizeof(P));
     P.row_begin = o->row_begin < 0 ? 0 : o->row_begin;
     P.row_end = (o->row_end <= 0 || o->row_end > c.height) ? c.height : o->row_end;
@@ -1395,6 +1407,113 @@ int rtg_render(rtg_scene* s, const rtg_render_opts* o, float* hdr_rgb, uint8_t* 
     }
     if (tonemap && n > 1 && ldr_rgb) return rtg_tonemap(hdr, cam.width, cam.height, &tp, ldr_rgb, s->device);
     return RTG_OK;
+}
+
+// ---- ray queries (rtg_query.hip)
+static int query_args(const rtg_scene* s, const void* rays, int64_t n, uint32_t flags, const void* hits) {
+    if (!s) return set_err(RTG_ERR_INVALID, "null scene");
+    if (n < 0 || n > INT32_MAX) return set_err(RTG_ERR_INVALID, "%lld rays: at most INT32_MAX per call", (long long)n);
+    if (flags & ~(uint32_t)(RTG_QUERY_ANY_HIT | RTG_QUERY_COHERENT))
+        return set_err(RTG_ERR_INVALID, "unknown query flags 0x%x", flags);
+    if (n > 0 && (!rays || !hits)) return set_err(RTG_ERR_INVALID, "null buffer");
+    return RTG_OK;
+}
+
+int rtg_trace_rays_device(rtg_scene* s, const rtg_ray* d_rays, int64_t n, uint32_t flags, rtg_hit* d_hits,
+                          float* d_normals, void* stream) {
+    int rc = query_args(s, d_rays, n, flags, d_hits);
+    if (rc || n == 0) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(rtg::launch_query(s->ds, s->feat, d_rays, (int)n, flags, d_hits,
+                              (flags & RTG_QUERY_ANY_HIT) ? nullptr : (float4*)d_normals, (hipStream_t)stream));
+    return RTG_OK;
+}
+
+// the host-buffer queries' scratch buffer `k` (rtg_scene::q_mem) of at least `bytes`
+static int query_scratch(rtg_scene* s, int k, size_t bytes) {
+    if (s->q_cap[k] >= bytes) return RTG_OK;
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    if (s->q_mem[k]) { (void)hipFree(s->q_mem[k]); s->q_mem[k] = nullptr; }
+    s->q_cap[k] = 0;
+    if (hipMalloc(&s->q_mem[k], bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return set_err(RTG_ERR_NOMEM, "query scratch of %zu bytes", bytes);
+    }
+    s->q_cap[k] = bytes;
+    return RTG_OK;
+}
+
+int rtg_trace_rays(rtg_scene* s, const rtg_ray* rays, int64_t n, uint32_t flags, rtg_hit* hits, float* normals) {
+    int rc = query_args(s, rays, n, flags, hits);
+    if (rc || n == 0) return rc;
+    if (flags & RTG_QUERY_ANY_HIT) normals = nullptr;
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t N = (size_t)n;
+    if ((rc = query_scratch(s, 0, N * sizeof(rtg_ray)))) return rc;
+    if ((rc = query_scratch(s, 1, N * sizeof(rtg_hit)))) return rc;
+    if (normals && (rc = query_scratch(s, 2, N * 4 * sizeof(float)))) return rc;
+    rtg_ray* dr = (rtg_ray*)s->q_mem[0];
+    rtg_hit* dh = (rtg_hit*)s->q_mem[1];
+    float4* dn = normals ? (float4*)s->q_mem[2] : nullptr;
+    HIP_TRY(hipMemcpyAsync(dr, rays, N * sizeof(rtg_ray), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(rtg::launch_query(s->ds, s->feat, dr, (int)n, flags, dh, dn, s->stream));
+    HIP_TRY(hipMemcpyAsync(hits, dh, N * sizeof(rtg_hit), hipMemcpyDeviceToHost, s->stream));
+    if (normals) HIP_TRY(hipMemcpyAsync(normals, dn, N * 4 * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return RTG_OK;
+}
+
+// the camera record and row range of a camera-ray batch
+static int camera_rays_args(const rtg_scene* s, const rtg_render_opts* o, const void* rays, rtg::DevCamera& C,
+                            int& row_begin, int& row_end) {
+    if (!s || !o || !rays) return set_err(RTG_ERR_INVALID, "null argument");
+    if (o->camera < 0 || o->camera >= (int)s->cameras.size()) return set_err(RTG_ERR_INVALID, "bad camera %d", o->camera);
+    const rtg_camera& c = s->cameras[o->camera];
+    if (c.width <= 0 || c.height <= 0) return set_err(RTG_ERR_INVALID, "camera %d has an empty image", o->camera);
+    dev_camera(c, C);
+    row_begin = o->row_begin < 0 ? 0 : o->row_begin;
+    row_end = (o->row_end <= 0 || o->row_end > c.height) ? c.height : o->row_end;
+    if (row_begin >= row_end) return set_err(RTG_ERR_INVALID, "empty row range");
+    if ((int64_t)c.width * c.height > INT32_MAX) return set_err(RTG_ERR_INVALID, "image of more than INT32_MAX pixels");
+    return RTG_OK;
+}
+
+int rtg_camera_rays_device(rtg_scene* s, const rtg_render_opts* o, rtg_ray* d_rays, void* stream) {
+    rtg::DevCamera C;
+    int rb, re;
+    int rc = camera_rays_args(s, o, d_rays, C, rb, re);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(rtg::launch_camera_rays(C, rb, re, o->sample_begin < 0 ? 0 : o->sample_begin, o->seed, d_rays,
+                                    (hipStream_t)stream));
+    return RTG_OK;
+}
+
+int rtg_camera_rays(rtg_scene* s, const rtg_render_opts* o, rtg_ray* rays) {
+    rtg::DevCamera C;
+    int rb, re;
+    int rc = camera_rays_args(s, o, rays, C, rb, re);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t bytes = (size_t)(re - rb) * C.width * sizeof(rtg_ray);
+    if ((rc = query_scratch(s, 0, bytes))) return rc;
+    HIP_TRY(rtg::launch_camera_rays(C, rb, re, o->sample_begin < 0 ? 0 : o->sample_begin, o->seed,
+                                    (rtg_ray*)s->q_mem[0], s->stream));
+    HIP_TRY(hipMemcpyAsync(rays, s->q_mem[0], bytes, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return RTG_OK;
+}
+
+int rtg_desc_trace_rays(const rtg_scene_desc* d, const rtg_ray* rays, int64_t n, uint32_t flags, rtg_hit* hits,
+                        float* normals) {
+    std::string err;
+    int rc;
+    try {
+        rc = rtg::host_trace_rays(d, rays, n, flags, hits, normals, err);
+    } catch (const std::exception& e) {
+        return set_err(RTG_ERR_NOMEM, "rtg_desc_trace_rays: %s", e.what());
+    }
+    return rc == RTG_OK ? RTG_OK : set_err(rc, "%s", err.c_str());
 }
 
 int rtg_host_alloc(size_t bytes, void** out) {

@@ -61,6 +61,13 @@ hipError_t build_mesh_bvh(const rtg_face* d_faces, int n, const float root_mn[3]
                           int faceOff, int nodeBase, float4* d_nodes, int2* d_ext, float4* d_tris, float4* d_fn,
                           float2* d_fuv, float4* d_v12, int* d_perm, int* nodeCount, bool* bigleaf,
                           hipStream_t st);
+// ray queries (rtg_query.hip): one ray per lane.  launch_query: closest hit (IntersectObjects) or,
+// with RTG_QUERY_ANY_HIT, occlusion (CastShadowRay) of n rays; normals nullable (closest hit only).
+// launch_camera_rays: the camera rays of rows [row_begin, row_end) at `sample`, in pixel order.
+hipError_t launch_query(const DevScene& S, int feat, const rtg_ray* rays, int n, uint32_t flags, rtg_hit* hits,
+                        float4* normals, hipStream_t stream);
+hipError_t launch_camera_rays(const DevCamera& C, int row_begin, int row_end, int sample, unsigned long long seed,
+                              rtg_ray* rays, hipStream_t stream);
 enum { WAVE_STAGES = 4, MEGA_STAGES = 1, TREE_STAGES = 2, PATH_STAGES = 1, MAX_STAGES = 4 };
 // Timed stage layouts (RTG_RENDER_TIMING): which kernels ran between the recorded events.
 enum { LAYOUT_WAVE = 0,          // k_primary, k_shade, k_shadow, k_resolve

@@ -33,6 +33,12 @@ RTG_RENDER_EXACT_SHADOW = 32
 RTG_RENDER_ORDERED = 64
 RTG_RENDER_SAMPLE_PASSES = 128
 RTG_LOAD_DEVICE_BVH = 1
+RTG_QUERY_ANY_HIT = 1
+RTG_QUERY_COHERENT = 2
+# rtg_ray (32 B) and rtg_hit (16 B) as NumPy structured dtypes
+RAY_DTYPE = np.dtype([("ox", "<f4"), ("oy", "<f4"), ("oz", "<f4"), ("tmax", "<f4"),
+                      ("dx", "<f4"), ("dy", "<f4"), ("dz", "<f4"), ("time", "<f4")])
+HIT_DTYPE = np.dtype([("t", "<f4"), ("object", "<i4"), ("face", "<i4"), ("pad", "<i4")])
 RTG_CAMERA_SIZE = 392   # sizeof(rtg_camera), checked against the C compiler by tests/test_abi.py
 
 
@@ -98,6 +104,7 @@ EXPORTED = [
     "rtg_last_error", "rtg_abi_version",
     "rtg_scene_create_multi", "rtg_scene_num_devices", "rtg_part_runs", "rtg_copy_part_to_host",
     "rtg_host_alloc", "rtg_host_free", "rtg_host_register", "rtg_host_unregister",
+    "rtg_trace_rays_device", "rtg_trace_rays", "rtg_camera_rays_device", "rtg_camera_rays", "rtg_desc_trace_rays",
 ]
 
 _lib = None
@@ -156,6 +163,11 @@ def lib() -> ctypes.CDLL:
     L.rtg_host_free.argtypes = [vp]
     L.rtg_host_register.argtypes = [vp, ctypes.c_size_t]
     L.rtg_host_unregister.argtypes = [vp]
+    L.rtg_trace_rays_device.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_uint32, vp, vp, vp]
+    L.rtg_trace_rays.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_uint32, vp, vp]
+    L.rtg_camera_rays_device.argtypes = [vp, P(RenderOpts), vp, vp]
+    L.rtg_camera_rays.argtypes = [vp, P(RenderOpts), vp]
+    L.rtg_desc_trace_rays.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_uint32, vp, vp]
     _lib = L
     return L
 
@@ -163,6 +175,33 @@ def lib() -> ctypes.CDLL:
 def _check(rc: int):
     if rc != 0:
         raise RTGError(rc, lib().rtg_last_error().decode(errors="replace"))
+
+
+def make_rays(origins, directions, tmax=np.inf, time=0.0) -> np.ndarray:
+    """(n, 3) origins and directions (+ scalar or (n,) tmax / time) -> RAY_DTYPE array."""
+    o = np.asarray(origins, np.float32).reshape(-1, 3)
+    d = np.asarray(directions, np.float32).reshape(-1, 3)
+    rays = np.zeros(len(o), RAY_DTYPE)
+    rays["ox"], rays["oy"], rays["oz"] = o[:, 0], o[:, 1], o[:, 2]
+    rays["dx"], rays["dy"], rays["dz"] = d[:, 0], d[:, 1], d[:, 2]
+    rays["tmax"] = tmax
+    rays["time"] = time
+    return rays
+
+
+def _query_flags(any_hit: bool, coherent: bool) -> int:
+    return (RTG_QUERY_ANY_HIT if any_hit else 0) | (RTG_QUERY_COHERENT if coherent else 0)
+
+
+def _query(fn, handle, rays, any_hit, coherent, normals):
+    """Shared body of HostScene.trace / DeviceScene.trace: hits, or (hits, normals (n, 4))."""
+    rays = np.ascontiguousarray(rays, RAY_DTYPE)
+    n = rays.size
+    hits = np.zeros(n, HIT_DTYPE)
+    nrm = np.zeros((n, 4), np.float32) if normals else None
+    _check(fn(handle, rays.ctypes.data, n, _query_flags(any_hit, coherent), hits.ctypes.data,
+              nrm.ctypes.data if normals else None))
+    return (hits, nrm) if normals else hits
 
 
 def device_count() -> int:
@@ -212,6 +251,12 @@ class HostScene:
         _check(lib().rtg_desc_anyhit_check(self.desc, mode, out, 8))
         keys = ("nodes", "entries", "depth", "leaf_prims", "face_prims", "exact_faces", "violations", "built")
         return dict(zip(keys, (int(x) for x in out)))
+
+    def trace(self, rays, any_hit: bool = False, coherent: bool = False, normals: bool = False):
+        """Ray queries on the host, no device (rtg_desc_trace_rays: the reference's object loop
+        restated plainly -- the yardstick of DeviceScene.trace).  rays: RAY_DTYPE array.  Returns
+        the HIT_DTYPE array, or (hits, normals (n, 4) float32) with ``normals=True``."""
+        return _query(lib().rtg_desc_trace_rays, self.desc, rays, any_hit, coherent, normals)
 
     def num_cameras(self) -> int:
         n = 0
@@ -288,6 +333,40 @@ class DeviceScene:
         o = self.opts(camera, 0, -1, rows, 0, 0, part)
         _check(lib().rtg_copy_part_to_host(self._s, ctypes.byref(o), d_hdr or None, d_ldr or None, h_hdr or None,
                                            h_ldr or None, stream or None))
+
+    def trace(self, rays, any_hit: bool = False, coherent: bool = False, normals: bool = False):
+        """Ray queries on host arrays (rtg_trace_rays; synchronous).  rays: RAY_DTYPE array.
+        Closest hit: t / object / face per ray (a miss: object = face = -1, t = tmax); with
+        ``any_hit`` occlusion (object 0 / -1; emissive meshes skipped, time ignored).
+        ``coherent`` is a performance hint (64 consecutive rays are similar), never a different
+        answer.  Returns the HIT_DTYPE array, or (hits, normals (n, 4) float32) with
+        ``normals=True`` (world-space unit geometric normals; zeros for a miss)."""
+        return _query(lib().rtg_trace_rays, self._s, rays, any_hit, coherent, normals)
+
+    def trace_device(self, rays_ptr: int, n: int, hits_ptr: int, normals_ptr: int = 0, stream: int = 0,
+                     flags: int = 0):
+        """Asynchronous ray queries on device buffers (e.g. torch tensor data_ptr()s: n x 32 B
+        rays, n x 16 B hits, optionally n x 4 float32 normals) on ``stream``; flags RTG_QUERY_*."""
+        _check(lib().rtg_trace_rays_device(self._s, rays_ptr or None, n, flags, hits_ptr or None,
+                                           normals_ptr or None, stream or None))
+
+    def camera_rays(self, camera: int = 0, rows=(0, 0), sample: int = 0, seed: int = 0x5EED) -> np.ndarray:
+        """The rays render() traces for ``camera`` at sample index ``sample`` and ``seed``, rows
+        ``rows`` in pixel order (rtg_camera_rays): RAY_DTYPE array, tmax = inf, time = the
+        motion-blur draw."""
+        c = self.host.camera(camera)
+        r0 = max(rows[0], 0)
+        r1 = c["height"] if rows[1] <= 0 or rows[1] > c["height"] else rows[1]
+        rays = np.zeros(max(r1 - r0, 0) * c["width"], RAY_DTYPE)
+        o = self.opts(camera, sample, 1, rows, 0, seed)
+        _check(lib().rtg_camera_rays(self._s, ctypes.byref(o), rays.ctypes.data))
+        return rays
+
+    def camera_rays_device(self, rays_ptr: int, camera: int = 0, rows=(0, 0), sample: int = 0, seed: int = 0x5EED,
+                           stream: int = 0):
+        """camera_rays() into a device buffer (width x rows x 32 B) on ``stream``; asynchronous."""
+        o = self.opts(camera, sample, 1, rows, 0, seed)
+        _check(lib().rtg_camera_rays_device(self._s, ctypes.byref(o), rays_ptr or None, stream or None))
 
     def export_bvh(self):
         """(nodes (N, 8) float32, tris (F, 12) float32): the device's walk records."""

@@ -427,6 +427,63 @@ int rtg_scene_timings(rtg_scene* scene, float* ms, const char** names, int32_t c
 int rtg_scene_timed_samples(const rtg_scene* scene, int32_t* samples);
 
 /* ------------------------------------------------------------------------- */
+/* Ray queries: closest hit, occlusion, camera-ray batches.  Added symbols    */
+/* only -- RTG_ABI_VERSION stays 6 (nothing existing changed layout or        */
+/* meaning).                                                                  */
+/* ------------------------------------------------------------------------- */
+/* 32 B: two 16-byte loads per ray */
+typedef struct {
+    float ox, oy, oz, tmax;   /* tmax: the walk's initial minT; INFINITY = unbounded */
+    float dx, dy, dz, time;   /* time: the reference's motion-blur time in [0,1) */
+} rtg_ray;
+/* 16 B: one 16-byte store per hit */
+typedef struct { float t; int32_t object; int32_t face; int32_t pad; } rtg_hit;
+enum rtg_query_flags {
+    RTG_QUERY_ANY_HIT = 1,    /* occlusion instead of closest hit */
+    RTG_QUERY_COHERENT = 2    /* hint: 64 consecutive rays are similar (e.g. camera rays) */
+};
+
+/* Semantics (the reference's own, raytracer.cpp:585-643):
+ *  - Closest hit: the result of IntersectObjects with its initial minT set to tmax.  t is the
+ *    accepted distance, object the index into objects[], face the global index into faces[] in
+ *    BVH order (the order rtg_scene_export_bvh reports; -1 for a sphere).  A miss is
+ *    object = face = -1 with t = tmax.  Ties and the strict t < minT are the reference's: among
+ *    equal distances the first object, and within a mesh the first face its BVH walk meets, win.
+ *    Like the reference's ray, a motion-blurred instance whose world box is missed leaves its
+ *    offset on the origin the later objects see.
+ *  - RTG_QUERY_ANY_HIT: CastShadowRay's boolean with minT0 = limit = tmax: object is 0 if
+ *    occluded and -1 if not; t and face are unspecified.  As in the reference, objects flagged
+ *    RTG_OBJF_SHADOW_SKIP (emissive meshes) are skipped and `time` is ignored (shadow rays
+ *    carry time 0).
+ *  - normals (closest hit only; nullable; 4 floats per ray): the world-space unit normal of the
+ *    hit -- the face's or sphere's normal through the object's inverse transpose, as the
+ *    reference computes it before any normal or bump map -- with a fourth component of 0; a
+ *    miss gives all zeros.  Ignored with RTG_QUERY_ANY_HIT.
+ *  - RTG_QUERY_COHERENT is a performance hint only: results are bit-identical with and
+ *    without it.
+ *  - n == 0 is RTG_OK; n above INT32_MAX or a null buffer is RTG_ERR_INVALID. */
+
+/* Device-resident buffers on `stream`; asynchronous like rtg_render_device, no allocation per
+ * call.  A multi-device scene answers on its first replica. */
+int rtg_trace_rays_device(rtg_scene* scene, const rtg_ray* d_rays, int64_t n, uint32_t flags, rtg_hit* d_hits,
+                          float* d_normals, void* stream);
+/* Same on host buffers (synchronous). */
+int rtg_trace_rays(rtg_scene* scene, const rtg_ray* rays, int64_t n, uint32_t flags, rtg_hit* hits,
+                   float* normals);
+/* The rays rtg_render traces for opts->camera: rows [row_begin, row_end) (row_end <= 0: all),
+ * sample opts->sample_begin, in pixel order (width * rows rays), each from the RNG key of
+ * (opts->seed, pixel, sample) -- GenerateRay's ray, depth-of-field and motion-blur draws
+ * included.  tmax is INFINITY and time the motion-blur draw.  The other fields of opts are
+ * ignored. */
+int rtg_camera_rays_device(rtg_scene* scene, const rtg_render_opts* opts, rtg_ray* d_rays, void* stream);
+int rtg_camera_rays(rtg_scene* scene, const rtg_render_opts* opts, rtg_ray* rays);
+/* Host only, no device: the reference's object loop restated plainly (recursive BVH descent
+ * over the description's own nodes) -- the yardstick of the device queries, bit for bit.
+ * RTG_ERR_INVALID for a description without nodes (RTG_LOAD_DEVICE_BVH). */
+int rtg_desc_trace_rays(const rtg_scene_desc* desc, const rtg_ray* rays, int64_t n, uint32_t flags,
+                        rtg_hit* hits, float* normals);
+
+/* ------------------------------------------------------------------------- */
 /* Tonemapping (tonemapper.h, main.cpp:187-192)                               */
 /* ------------------------------------------------------------------------- */
 /* Tonemapper(opType, keyValue, burnPerct, saturation, gamma) (tonemapper.h:18-25);
