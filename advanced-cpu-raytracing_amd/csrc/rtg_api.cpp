@@ -146,10 +146,11 @@ struct rtg_scene {
     float* d_hdr = nullptr;
     unsigned char* d_ldr = nullptr;
     size_t d_pixels = 0;
-    // scratch of the host-buffer ray queries (rtg_trace_rays, rtg_camera_rays): rays, hits,
-    // normals; grown on demand, never touched by the device-buffer entry points
-    void* q_mem[3] = {};
-    size_t q_cap[3] = {};
+    // scratch of the host-buffer ray queries (rtg_trace_rays, rtg_camera_rays, rtg_radiance_rays):
+    // rays, hits, normals, radiance output, pixel ids; grown on demand, never touched by the
+    // device-buffer entry points
+    void* q_mem[5] = {};
+    size_t q_cap[5] = {};
     // block -> tile tables, one per (tiles_x, tiles_y) met (never re-uploaded: kernels of
     // several streams may be reading them)
     std::vector<std::unique_ptr<TileMap>> tile_maps;
@@ -1500,6 +1501,69 @@ int rtg_camera_rays(rtg_scene* s, const rtg_render_opts* o, rtg_ray* rays) {
     HIP_TRY(rtg::launch_camera_rays(C, rb, re, o->sample_begin < 0 ? 0 : o->sample_begin, o->seed,
                                     (rtg_ray*)s->q_mem[0], s->stream));
     HIP_TRY(hipMemcpyAsync(rays, s->q_mem[0], bytes, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return RTG_OK;
+}
+
+// ---- radiance queries (rtg_radiance.hip)
+// the camera record and kernel parameters of a radiance batch; host_ids: pixel ids in host memory
+static int radiance_args(const rtg_scene* s, const rtg_radiance_opts* o, const void* rays, const int32_t* host_ids,
+                         int64_t n, const void* rgbt, rtg::DevCamera& C, rtg::RadianceParams& P) {
+    if (!o) return set_err(RTG_ERR_INVALID, "null options");
+    if (n < 0 || n > INT32_MAX) return set_err(RTG_ERR_INVALID, "%lld rays: at most INT32_MAX per call", (long long)n);
+    if (o->flags & ~(uint32_t)RTG_RADIANCE_CAMERA_EYE) return set_err(RTG_ERR_INVALID, "unknown radiance flags 0x%x", o->flags);
+    if (o->first_pixel < 0) return set_err(RTG_ERR_INVALID, "negative first_pixel %d", o->first_pixel);
+    if (n > 0 && (!rays || !rgbt)) return set_err(RTG_ERR_INVALID, "null buffer");
+    if (!s) return set_err(RTG_ERR_INVALID, "null scene");
+    if (o->camera < 0 || o->camera >= (int)s->cameras.size()) return set_err(RTG_ERR_INVALID, "bad camera %d", o->camera);
+    const rtg_camera& c = s->cameras[o->camera];
+    if (c.width <= 0 || c.height <= 0) return set_err(RTG_ERR_INVALID, "camera %d has an empty image", o->camera);
+    if (host_ids)
+        for (int64_t i = 0; i < n; ++i)
+            if (host_ids[i] < 0) return set_err(RTG_ERR_INVALID, "negative pixel id %d at ray %lld", host_ids[i], (long long)i);
+    // the frame stack's depth: rtg_scene_create's own bound, kept with the kernel that relies on it
+    if (s->max_depth > rtg::max_supported_depth())
+        return set_err(RTG_ERR_UNSUPPORTED, "MaxRecursionDepth %d > %d", s->max_depth, rtg::max_supported_depth());
+    dev_camera(c, C);
+    std::memset(&P, 0, sizeof(P));
+    P.n = (int)n;
+    P.first_pixel = o->first_pixel;
+    P.sample_begin = o->sample_begin < 0 ? 0 : o->sample_begin;
+    P.sample_count = o->sample_count <= 0 ? 1 : o->sample_count;
+    P.camera_eye = (o->flags & RTG_RADIANCE_CAMERA_EYE) ? 1 : 0;
+    P.seed = o->seed;
+    return RTG_OK;
+}
+
+int rtg_radiance_rays_device(rtg_scene* s, const rtg_radiance_opts* o, const rtg_ray* d_rays, const int32_t* d_pixel_ids,
+                             int64_t n, float* d_rgbt, void* stream) {
+    rtg::DevCamera C;
+    rtg::RadianceParams P;
+    int rc = radiance_args(s, o, d_rays, nullptr, n, d_rgbt, C, P);
+    if (rc || n == 0) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(rtg::launch_radiance(s->ds, C, P, s->shade_sk, s->feat, d_rays, d_pixel_ids, d_rgbt, (hipStream_t)stream));
+    return RTG_OK;
+}
+
+int rtg_radiance_rays(rtg_scene* s, const rtg_radiance_opts* o, const rtg_ray* rays, const int32_t* pixel_ids, int64_t n,
+                      float* rgbt) {
+    rtg::DevCamera C;
+    rtg::RadianceParams P;
+    int rc = radiance_args(s, o, rays, pixel_ids, n, rgbt, C, P);
+    if (rc || n == 0) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t N = (size_t)n;
+    if ((rc = query_scratch(s, 0, N * sizeof(rtg_ray)))) return rc;
+    if ((rc = query_scratch(s, 3, N * 4 * sizeof(float)))) return rc;
+    if (pixel_ids && (rc = query_scratch(s, 4, N * sizeof(int32_t)))) return rc;
+    rtg_ray* dr = (rtg_ray*)s->q_mem[0];
+    float* dc = (float*)s->q_mem[3];
+    int32_t* di = pixel_ids ? (int32_t*)s->q_mem[4] : nullptr;
+    HIP_TRY(hipMemcpyAsync(dr, rays, N * sizeof(rtg_ray), hipMemcpyHostToDevice, s->stream));
+    if (di) HIP_TRY(hipMemcpyAsync(di, pixel_ids, N * sizeof(int32_t), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(rtg::launch_radiance(s->ds, C, P, s->shade_sk, s->feat, dr, di, dc, s->stream));
+    HIP_TRY(hipMemcpyAsync(rgbt, dc, N * 4 * sizeof(float), hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
     return RTG_OK;
 }

@@ -68,6 +68,18 @@ hipError_t launch_query(const DevScene& S, int feat, const rtg_ray* rays, int n,
                         float4* normals, hipStream_t stream);
 hipError_t launch_camera_rays(const DevCamera& C, int row_begin, int row_end, int sample, unsigned long long seed,
                               rtg_ray* rays, hipStream_t stream);
+// radiance queries (rtg_radiance.hip): the fused kernel's ray tree below n caller rays, one ray per
+// lane; ray i plays pixel ids ? ids[i] : first_pixel + i (RNG key, background-texture lookup).
+// Of C: the renderer flags, width / height and -- with camera_eye -- the position.  sk / feat as
+// for launch_mega.  rgbt: 4 floats per ray (colour, the primary hit's t).
+struct RadianceParams {
+    int n, first_pixel;
+    int sample_begin, sample_count;
+    int camera_eye, pad0;
+    unsigned long long seed;
+};
+hipError_t launch_radiance(const DevScene& S, const DevCamera& C, const RadianceParams& P, int sk, int feat,
+                           const rtg_ray* rays, const int* ids, float* rgbt, hipStream_t stream);
 enum { WAVE_STAGES = 4, MEGA_STAGES = 1, TREE_STAGES = 2, PATH_STAGES = 1, MAX_STAGES = 4 };
 // Timed stage layouts (RTG_RENDER_TIMING): which kernels ran between the recorded events.
 enum { LAYOUT_WAVE = 0,          // k_primary, k_shade, k_shadow, k_resolve

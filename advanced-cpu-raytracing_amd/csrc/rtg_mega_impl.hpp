@@ -17,13 +17,38 @@ namespace rtg {
 // shared with the wavefront path-tracing pipeline.
 // SK / FEAT: the scene's shading and traversal features (a superset; the path-tracing
 // variants of rtg_mega_pt.hip), everything by default.
-template <int MAXD, bool STATS, bool PT, int SK = SK_ALL, int FEAT = FEAT_ALL>
-DEV f3 render_sample(const DevScene& S, const DevCamera& C, int px, int py, uint64_t key, Cnt<STATS>& cn) {
+// SRC: where the primary ray comes from.  CameraRay (a render): GenerateRay's ray of the pixel,
+// unbounded, its primary hit seen from the camera's position (also for depth-of-field rays).
+// GivenRay (radiance queries, render_ray below): a caller's ray -- `tmax` bounds the primary ray
+// only (the walk's initial minT), `eye` is the viewer of the primary hit, *tprim receives the
+// primary ray's accepted distance (tmax on a miss); of C the tree then reads the renderer flags
+// and, in miss_color, width / height, (px, py) being the pixel of the background-texture lookup.
+// The split is compile-time so that k_render compiles to what it was without it
+// (profiles/r08_render_resources.txt).
+struct CameraRay { static constexpr bool given = false; };
+struct GivenRay {
+    static constexpr bool given = true;
+    Ray ray;
+    float mbTime, tmax;
+    f3 eye;
+    float* tprim;
+};
+
+template <int MAXD, bool STATS, bool PT, int SK = SK_ALL, int FEAT = FEAT_ALL, class SRC = CameraRay>
+DEV f3 render_sample(const DevScene& S, const DevCamera& C, int px, int py, uint64_t key, Cnt<STATS>& cn,
+                     const SRC src = SRC()) {
     float mbTime;
     Pending p;
-    p.R = camera_ray(C, px, py, key, mbTime);
-    const f3 cpos = ld3(C.pos);
-    cn.cam();
+    f3 cpos;
+    if constexpr (SRC::given) {
+        p.R = src.ray;
+        mbTime = src.mbTime;
+        cpos = src.eye;
+    } else {
+        p.R = camera_ray(C, px, py, key, mbTime);
+        cpos = ld3(C.pos);
+        cn.cam();
+    }
     p.medium = 1.0f;
     p.depth = S.max_depth;
     p.key = key;
@@ -37,7 +62,12 @@ DEV f3 render_sample(const DevScene& S, const DevCamera& C, int px, int py, uint
     v.medium = 1.f;
     for (;;) {
         Node cur;
-        const bool hit = trace<false, STATS, FEAT>(S, p.R, mbTime, INFINITY, INFINITY, cur.h, cn);
+        float minT = INFINITY;
+        if constexpr (SRC::given) minT = p.pend == 0 ? src.tmax : INFINITY;
+        const bool hit = trace<false, STATS, FEAT>(S, p.R, mbTime, minT, INFINITY, cur.h, cn);
+        if constexpr (SRC::given) {
+            if (p.pend == 0) *src.tprim = cur.h.t;
+        }
         if (p.pend == 0 && !hit) return miss_color<SK>(S, C, px, py, p.R.d);
         if constexpr (PT) {
             if (p.pend == 3) stack[GIDX(S, sp - 1, MAXD, 9)].skip = emissive_hit_id(S, cur.h, hit);
@@ -77,6 +107,13 @@ DEV f3 render_sample(const DevScene& S, const DevCamera& C, int px, int py, uint
         }
         if (!descended) return v.value;
     }
+}
+
+// The ray tree below a given primary ray (k_radiance): render_sample from the loop on.
+template <int MAXD, bool STATS, bool PT, int SK = SK_ALL, int FEAT = FEAT_ALL>
+DEV f3 render_ray(const DevScene& S, const DevCamera& C, const Ray& ray, float mbTime, float tmax, f3 eye, int px, int py,
+                  uint64_t key, Cnt<STATS>& cn, float& tprim) {
+    return render_sample<MAXD, STATS, PT, SK, FEAT, GivenRay>(S, C, px, py, key, cn, GivenRay{ray, mbTime, tmax, eye, &tprim});
 }
 
 template <int MAXD, bool STATS, bool PT, int SK = SK_ALL, int FEAT = FEAT_ALL>

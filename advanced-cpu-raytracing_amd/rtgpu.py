@@ -35,6 +35,7 @@ RTG_RENDER_SAMPLE_PASSES = 128
 RTG_LOAD_DEVICE_BVH = 1
 RTG_QUERY_ANY_HIT = 1
 RTG_QUERY_COHERENT = 2
+RTG_RADIANCE_CAMERA_EYE = 1
 # rtg_ray (32 B) and rtg_hit (16 B) as NumPy structured dtypes
 RAY_DTYPE = np.dtype([("ox", "<f4"), ("oy", "<f4"), ("oz", "<f4"), ("tmax", "<f4"),
                       ("dx", "<f4"), ("dy", "<f4"), ("dz", "<f4"), ("time", "<f4")])
@@ -82,6 +83,19 @@ class RenderOpts(ctypes.Structure):
     ]
 
 
+class RadianceOpts(ctypes.Structure):
+    """rtg_radiance_opts (32 B)."""
+    _fields_ = [
+        ("camera", ctypes.c_int32),
+        ("sample_begin", ctypes.c_int32),
+        ("sample_count", ctypes.c_int32),
+        ("flags", ctypes.c_uint32),
+        ("seed", ctypes.c_uint64),
+        ("first_pixel", ctypes.c_int32),
+        ("pad0", ctypes.c_int32),
+    ]
+
+
 class Stats(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint64) for n in (
         "camera_rays", "secondary_rays", "shadow_rays", "node_visits", "tri_tests",
@@ -105,6 +119,7 @@ EXPORTED = [
     "rtg_scene_create_multi", "rtg_scene_num_devices", "rtg_part_runs", "rtg_copy_part_to_host",
     "rtg_host_alloc", "rtg_host_free", "rtg_host_register", "rtg_host_unregister",
     "rtg_trace_rays_device", "rtg_trace_rays", "rtg_camera_rays_device", "rtg_camera_rays", "rtg_desc_trace_rays",
+    "rtg_radiance_rays_device", "rtg_radiance_rays",
 ]
 
 _lib = None
@@ -168,6 +183,8 @@ def lib() -> ctypes.CDLL:
     L.rtg_camera_rays_device.argtypes = [vp, P(RenderOpts), vp, vp]
     L.rtg_camera_rays.argtypes = [vp, P(RenderOpts), vp]
     L.rtg_desc_trace_rays.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_uint32, vp, vp]
+    L.rtg_radiance_rays_device.argtypes = [vp, P(RadianceOpts), vp, vp, ctypes.c_int64, vp, vp]
+    L.rtg_radiance_rays.argtypes = [vp, P(RadianceOpts), vp, vp, ctypes.c_int64, vp]
     _lib = L
     return L
 
@@ -367,6 +384,42 @@ class DeviceScene:
         """camera_rays() into a device buffer (width x rows x 32 B) on ``stream``; asynchronous."""
         o = self.opts(camera, sample, 1, rows, 0, seed)
         _check(lib().rtg_camera_rays_device(self._s, ctypes.byref(o), rays_ptr or None, stream or None))
+
+    @staticmethod
+    def radiance_opts(camera=0, sample=0, samples=1, seed=0x5EED, first_pixel=0, camera_eye=False) -> RadianceOpts:
+        return RadianceOpts(camera, sample, samples, RTG_RADIANCE_CAMERA_EYE if camera_eye else 0, seed, first_pixel, 0)
+
+    def radiance(self, rays, camera: int = 0, sample: int = 0, samples: int = 1, seed: int = 0x5EED, pixel_ids=None,
+                 first_pixel: int = 0, camera_eye: bool = False) -> np.ndarray:
+        """The colour the renderer computes along caller rays (rtg_radiance_rays; synchronous):
+        (n, 4) float32 -- unclamped rgb and the primary hit's t (tmax on a miss).  rays:
+        RAY_DTYPE array.  Ray i plays pixel ``pixel_ids[i]`` (or ``first_pixel + i``) of
+        ``camera``, which supplies the renderer flags and the image size of the background
+        texture and nothing else; sample ``s`` of it uses render()'s random numbers for that
+        pixel, sample and ``seed``.  ``samples`` > 1: the plain float mean of samples ``sample``
+        .. ``sample + samples - 1``, summed in ascending order.  Primary hits are shaded as seen
+        from the ray's origin, or from the camera's position with ``camera_eye`` (as render()
+        shades its depth-of-field rays): ``radiance(camera_rays(seed=s), seed=s,
+        camera_eye=True)`` is render()'s image of a one-sample camera bit for bit."""
+        rays = np.ascontiguousarray(rays, RAY_DTYPE)
+        n = rays.size
+        ids = None if pixel_ids is None else np.ascontiguousarray(pixel_ids, np.int32)
+        if ids is not None and ids.size != n:
+            raise ValueError(f"{ids.size} pixel ids for {n} rays")
+        out = np.zeros((n, 4), np.float32)
+        o = self.radiance_opts(camera, sample, samples, seed, first_pixel, camera_eye)
+        _check(lib().rtg_radiance_rays(self._s, ctypes.byref(o), rays.ctypes.data,
+                                       ids.ctypes.data if ids is not None else None, n, out.ctypes.data))
+        return out
+
+    def radiance_device(self, rays_ptr: int, n: int, out_ptr: int, ids_ptr: int = 0, stream: int = 0, camera: int = 0,
+                        sample: int = 0, samples: int = 1, seed: int = 0x5EED, first_pixel: int = 0,
+                        camera_eye: bool = False):
+        """Asynchronous radiance() on device buffers (e.g. torch tensor data_ptr()s: n x 32 B rays,
+        n x 4 float32 out, optionally n int32 pixel ids) on ``stream``; allocates nothing."""
+        o = self.radiance_opts(camera, sample, samples, seed, first_pixel, camera_eye)
+        _check(lib().rtg_radiance_rays_device(self._s, ctypes.byref(o), rays_ptr or None, ids_ptr or None, n,
+                                              out_ptr or None, stream or None))
 
     def export_bvh(self):
         """(nodes (N, 8) float32, tris (F, 12) float32): the device's walk records."""

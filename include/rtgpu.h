@@ -484,6 +484,63 @@ int rtg_desc_trace_rays(const rtg_scene_desc* desc, const rtg_ray* rays, int64_t
                         rtg_hit* hits, float* normals);
 
 /* ------------------------------------------------------------------------- */
+/* Radiance queries: the colour the renderer computes along caller-supplied   */
+/* rays.  Added symbols and types only -- RTG_ABI_VERSION stays 6.            */
+/* ------------------------------------------------------------------------- */
+enum rtg_radiance_flags {
+    RTG_RADIANCE_CAMERA_EYE = 1   /* primary hits are shaded as seen from the camera's position, not
+                                     from the ray's origin: the reference's own behaviour for its
+                                     depth-of-field rays (raytracer.cpp: PerformShading gets the camera
+                                     position, GenerateRay moved the origin onto the lens) */
+};
+typedef struct {
+    int32_t camera;        /* supplies the renderer flags (path tracing, NEE, importance sampling,
+                              Russian roulette), width/height for the background-texture lookup, and
+                              the eye under RTG_RADIANCE_CAMERA_EYE.  Nothing else of it is used. */
+    int32_t sample_begin;  /* first sample index (<0 = 0) */
+    int32_t sample_count;  /* samples per ray (<=0 = 1) */
+    uint32_t flags;        /* rtg_radiance_flags */
+    uint64_t seed;
+    int32_t first_pixel;   /* ray i plays pixel first_pixel + i when pixel_ids is NULL */
+    int32_t pad0;
+} rtg_radiance_opts;
+
+/* Semantics (RenderPixel's, raytracer.cpp:38-63, below a ray of the caller's instead of
+ * GenerateRay's):
+ *  - Pixel and key: ray i takes the role of pixel p = pixel_ids ? pixel_ids[i] : first_pixel + i.
+ *    Sample s of it draws its random numbers from the key of (seed, p, s), the key rtg_render
+ *    uses for that pixel and sample; equal (seed, p, s) and equal rays give equal colours.  The
+ *    only other use of p is the background texture of a primary ray that misses: it is looked up
+ *    at px = p % width, py = p / width of opts->camera's image, as in a render.  A negative p is
+ *    RTG_ERR_INVALID where the host can see it (first_pixel, pixel_ids of rtg_radiance_rays);
+ *    device-resident ids are the caller's responsibility.
+ *  - Primary ray: origin, direction and time are taken as given; time is the motion-blur time,
+ *    which the whole ray tree inherits as in a render.  tmax bounds the primary ray only (the
+ *    walk's initial minT, as for rtg_trace_rays); a render's is INFINITY, which rtg_camera_rays
+ *    writes.  The eye of a primary hit is the ray's origin, or the camera's position under
+ *    RTG_RADIANCE_CAMERA_EYE.
+ *  - Value: 4 floats per ray.  With one sample, rgb is RenderPixel's colour for the ray -- the
+ *    whole ray tree, every light, textures, the miss colour -- unclamped: what rtg_render stores in
+ *    hdr_rgb for a camera of one sample, bit for bit, when the rays are rtg_camera_rays' of the
+ *    same seed and RTG_RADIANCE_CAMERA_EYE is set.  With sample_count = k > 1,
+ *    rgb = (((0 + c_0) + c_1) + ... + c_{k-1}) / (float)k per component, in float, in ascending
+ *    sample order, c_j being the colour of sample sample_begin + j.  The Gaussian pixel-filter
+ *    weights belong to rtg_render's pixel loop and are not applied.  The fourth float is the
+ *    primary hit's t (the same for every sample); tmax on a miss.
+ *  - n == 0 is RTG_OK.  n above INT32_MAX, a null scene / opts / ray / output buffer, an unknown
+ *    flag bit or a bad camera index is RTG_ERR_INVALID.  Without a device: RTG_ERR_HIP.
+ *  - Always the fused kernel's walk (the pipelines rtg_render may choose give the same image). */
+
+/* Device-resident buffers on `stream`: asynchronous, no allocation, and no render state touched
+ * (work buffers, plans, events, counters, timings).  d_pixel_ids nullable.  A multi-device scene
+ * answers on its first replica. */
+int rtg_radiance_rays_device(rtg_scene* scene, const rtg_radiance_opts* opts, const rtg_ray* d_rays,
+                             const int32_t* d_pixel_ids, int64_t n, float* d_rgbt, void* stream);
+/* Same on host buffers (synchronous; copies through the scene's query scratch). */
+int rtg_radiance_rays(rtg_scene* scene, const rtg_radiance_opts* opts, const rtg_ray* rays,
+                      const int32_t* pixel_ids, int64_t n, float* rgbt);
+
+/* ------------------------------------------------------------------------- */
 /* Tonemapping (tonemapper.h, main.cpp:187-192)                               */
 /* ------------------------------------------------------------------------- */
 /* Tonemapper(opType, keyValue, burnPerct, saturation, gamma) (tonemapper.h:18-25);

@@ -13,7 +13,18 @@ renders: RTG_FRAME_KERNEL=0 splits the sample pass into k_primary + k_shade_shad
 RTG_RENDER_EXACT_SHADOW gives k_shadow with the reference walk).  k_primary is the yardstick of
 (a): the same walk on the same rays, with a 32-byte ray read in place of ray generation.
 
-    python tools/query_bench.py [--launches 50] [--reps 3] [--out FILE]
+    python tools/query_bench.py [--launches 50] [--reps 3] [--out FILE] [--sections query,radiance]
+
+The radiance section (rtg_radiance_rays_device, DeviceScene.radiance_device) runs on the same
+height field and on the path-tracing fixture tests/golden/scenes/pt_cornell.xml at its own size:
+the camera's rays, generated on the device, shaded
+
+  (r)  in pixel order    (r-tiled) in k_primary's 8x8-tile order, pixel ids alongside
+  (r-perm) randomly permuted, pixel ids alongside
+  (r-tiled general) as (r-tiled) with RTG_MEGA_GENERAL=1: the SK_ALL / FEAT_ALL instantiation
+
+against the yardstick of the same session: stage k_render of RTG_RENDER_FUSED | RTG_RENDER_TIMING
+renders -- the same ray trees, with ray generation in place of a 32-byte load.
 """
 import argparse
 import os
@@ -27,6 +38,105 @@ sys.path.insert(0, os.path.join(ROOT, "advanced-cpu-raytracing_amd"))
 import numpy as np  # noqa: E402
 
 
+def radiance_section(args, name, xml):
+    """Timings of one scene: lines of text."""
+    import torch
+
+    import rtgpu
+
+    hs = rtgpu.HostScene(xml)
+    ds = rtgpu.DeviceScene(hs, 0)
+    cam = hs.camera(0)
+    w, h = cam["width"], cam["height"]
+    n = w * h
+    dev = torch.device("cuda:0")
+    st = torch.cuda.current_stream().cuda_stream
+    rays = torch.empty((n, 8), dtype=torch.float32, device=dev)
+    out = torch.empty((n, 4), dtype=torch.float32, device=dev)
+    ds.camera_rays_device(rays.data_ptr(), stream=st)
+    torch.cuda.synchronize()
+    g = torch.Generator(device="cpu").manual_seed(1234)
+    perm = torch.randperm(n, generator=g)
+    # k_primary's wave shape (rtg_common.hpp tile_pixel): 64 consecutive rays = one 8x8 pixel tile
+    assert w % 8 == 0 and h % 8 == 0
+    yy, xx = np.divmod(np.arange(n), w)
+    key = (yy // 8) * (w // 8) * 64 + (xx // 8) * 64 + (yy % 8) * 8 + (xx % 8)
+    order = np.empty(n, np.int64)
+    order[key] = np.arange(n)
+    order = torch.from_numpy(order)
+    sets = {"pixel": (rays, None)}
+    for tag, idx in (("tiled", order), ("perm", perm)):
+        sets[tag] = (rays[idx.to(dev)].contiguous(), idx.to(torch.int32).to(dev))
+    cases = [("r  radiance, pixel order", "pixel", False), ("r-tiled radiance, 8x8 tiles", "tiled", False),
+             ("r-perm radiance, permuted", "perm", False), ("r-tiled general instantiation", "tiled", True)]
+
+    def run(which, general, k):
+        buf, ids = sets[which]
+        if general:
+            os.environ["RTG_MEGA_GENERAL"] = "1"
+        for _ in range(k):
+            ds.radiance_device(buf.data_ptr(), n, out.data_ptr(), ids_ptr=ids.data_ptr() if ids is not None else 0,
+                               stream=st, camera_eye=True)
+        os.environ.pop("RTG_MEGA_GENERAL", None)
+
+    hdr = torch.empty((h, w, 3), dtype=torch.float32, device=dev)
+
+    def k_render():
+        ds.render_device(hdr.data_ptr(), 0, stream=st, flags=rtgpu.RTG_RENDER_FUSED | rtgpu.RTG_RENDER_TIMING)
+        return ds.timings()["k_render"]
+
+    # the answers first: every order gives the fused render's image
+    k_render()
+    torch.cuda.synchronize()
+    want = hdr.reshape(-1, 3).clone()
+    for _, which, general in cases:
+        run(which, general, 1)
+        torch.cuda.synchronize()
+        ids = sets[which][1]
+        ref = want if ids is None else want[ids.long()]
+        assert torch.equal(out[:, :3].view(torch.int32), ref.view(torch.int32)), which
+    for _, which, general in cases:
+        run(which, general, args.warmup)
+    for _ in range(args.warmup):
+        k_render()
+    torch.cuda.synchronize()
+    ms = {c[0]: [] for c in cases}
+    kr = []
+    for _ in range(args.reps):
+        for label, which, general in cases:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            run(which, general, args.launches)
+            e1.record()
+            e1.synchronize()
+            ms[label].append(e0.elapsed_time(e1) / args.launches)
+        kr.append(float(np.median([k_render() for _ in range(args.launches)])))
+    lines = [f"radiance: {name} {w}x{h}, {n} rays, {args.launches} launches x {args.reps} interleaved repetitions "
+             f"(every order checked against the fused render bit for bit)",
+             f"{'case':40s} {'ms (median)':>12s} {'min':>8s} {'max':>8s} {'/ k_render':>10s}"]
+    lines.append(f"{'k_render (fused render, same session)':40s} {np.median(kr):12.4f} {min(kr):8.4f} {max(kr):8.4f} {1.0:10.3f}")
+    for label, _, _ in cases:
+        v = ms[label]
+        lines.append(f"{label:40s} {np.median(v):12.4f} {min(v):8.4f} {max(v):8.4f} {np.median(v) / np.median(kr):10.3f}")
+    spread = lambda v: (max(v) - min(v)) / np.median(v) * 100
+    lines.append(f"spread over the repetitions: k_render {spread(kr):.1f} %, " +
+                 ", ".join(f"{label.split()[0]} {spread(ms[label]):.1f} %" for label, _, _ in cases))
+    return lines
+
+
+def radiance_main(args):
+    import scenes
+
+    tmp = tempfile.mkdtemp(prefix="query_bench_")
+    lines = []
+    xml = scenes.synthetic_heightfield(tmp, K=args.K, width=args.width, height=args.height)
+    os.chdir(tmp)
+    lines += radiance_section(args, f"synthetic_heightfield K={args.K}", xml)
+    os.chdir(os.path.join(ROOT, "tests", "golden", "scenes"))
+    lines += radiance_section(args, "pt_cornell", "pt_cornell.xml")
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--launches", type=int, default=50)
@@ -36,9 +146,24 @@ def main():
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--sections", default="query,radiance")
     args = ap.parse_args()
     out = os.path.abspath(args.out) if args.out else None
+    sections = args.sections.split(",")
+    text = []
+    if "query" in sections:
+        text += query_main(args)
+    if "radiance" in sections:
+        text += radiance_main(args)
+    text = "\n".join(text)
+    print(text)
+    if out:
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        with open(out, "w") as f:
+            f.write(text + "\n")
 
+
+def query_main(args):
     import torch
 
     import rtgpu
@@ -139,12 +264,8 @@ def main():
     a, kp = ms[cases[0][0]], stages.get("k_primary", [float("nan")])
     lines.append(f"(a) / k_primary = {np.median(a) / np.median(kp):.3f}; spread of k_primary over the repetitions "
                  f"{(max(kp) - min(kp)) / np.median(kp) * 100:.1f} %, of (a) {(max(a) - min(a)) / np.median(a) * 100:.1f} %")
-    text = "\n".join(lines)
-    print(text)
-    if out:
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        with open(out, "w") as f:
-            f.write(text + "\n")
+    os.environ.pop("RTG_FRAME_KERNEL", None)
+    return lines
 
 
 if __name__ == "__main__":
