@@ -170,21 +170,49 @@ template <> struct Cnt<true> {
 // ---------------------------------------------------------------------------
 struct Ray {
     f3 o, d;
+    // A local ray that stands for the reference's product with an exactly-identity inverse
+    // transform (trav_ray skips the product; scenes without transforms never form it).  The
+    // product is not quite the identity: for the identity inverse, and only for it, every row
+    // ends in +0 * w, so a -0 component comes out as +0 (under any other matrix -- a translation's
+    // last column is -t -- a -0 can survive, and local_ray forms that product in full) -- and the
+    // slab test divides by it: for an origin in a box plane, 0 / 0 = NaN meets 1 / +0 = +inf (the
+    // box passes) where 1 / -0 = -inf fails it.  Only box_hit looks at this (a ray with a zero
+    // direction component is never on the fast path, and no face or sphere decision depends on
+    // the sign of a zero).
+    // (Normalising the direction once -- d + 0 where the local ray is made, or in box_hit without
+    // the laundering below, which the compiler hoists to the same place -- keeps three more
+    // VGPRs live through every walk, the caller still needing the world direction: k_primary's
+    // sphere variant went from no scratch to 20 B per lane and the headline from 0.251 to
+    // 0.258 ms.  As a flag read in the exact branch: 0.2441 against the parent's 0.2441 +- 0.0005.)
+    bool ident = false;
 };
+// the world ray as the local ray of an object under the identity transform
+DEV Ray ident_ray(const Ray& r) {
+    Ray lr = r;
+    lr.ident = true;
+    return lr;
+}
 
 // BoundingBox::doesIntersectWith (shape.hpp:78-100): true divisions, x-slab by
 // comparison, y/z by fmin/fmax (NaN-ignoring), accept iff tmax>0 && tmax>=tmin && tmin<minT.
 DEV bool box_hit(float mnx, float mny, float mnz, float mxx, float mxy, float mxz, const Ray& r, float minT) {
-    float tx1 = (mnx - r.o.x) / r.d.x;
-    float tx2 = (mxx - r.o.x) / r.d.x;
+    // (Ray::ident: x + 0 turns -0 into +0 and changes nothing else, as the skipped product does;
+    // x + -0 changes nothing at all.  The direction is laundered so that the sums stay here, in
+    // the rarely taken exact branch, instead of being hoisted into the walks' registers.)
+    float dx = r.d.x, dy = r.d.y, dz = r.d.z;
+    asm volatile("" : "+v"(dx), "+v"(dy), "+v"(dz));
+    const float zero = r.ident ? 0.0f : -0.0f;
+    dx += zero; dy += zero; dz += zero;
+    float tx1 = (mnx - r.o.x) / dx;
+    float tx2 = (mxx - r.o.x) / dx;
     float tmin = tx1, tmax = tx2;
     if (tx1 > tx2) { tmin = tx2; tmax = tx1; }
-    float ty1 = (mny - r.o.y) / r.d.y;
-    float ty2 = (mxy - r.o.y) / r.d.y;
+    float ty1 = (mny - r.o.y) / dy;
+    float ty2 = (mxy - r.o.y) / dy;
     tmin = fmaxf(tmin, fminf(ty1, ty2));
     tmax = fminf(tmax, fmaxf(ty1, ty2));
-    float tz1 = (mnz - r.o.z) / r.d.z;
-    float tz2 = (mxz - r.o.z) / r.d.z;
+    float tz1 = (mnz - r.o.z) / dz;
+    float tz2 = (mxz - r.o.z) / dz;
     tmin = fmaxf(tmin, fminf(tz1, tz2));
     tmax = fminf(tmax, fmaxf(tz1, tz2));
     return tmax > 0 && tmax >= tmin && tmin < minT;
@@ -1058,8 +1086,9 @@ DEV Ray local_ray(const DevObject& ob, const Ray& r, float mbTime) {
     return lr;
 }
 // Traversal-only variant: an exact identity transform changes at most the sign of a zero
-// component (1*x + 0*y + ...), which no box / triangle / sphere decision or t value
-// depends on, so it is skipped.  Shading (surface()) always applies the full transform.
+// component (1*x + 0*y + ...), which no triangle / sphere decision or t value depends on, so it
+// is skipped; the exact slab test does depend on it and is told (Ray::ident).  Shading
+// (surface()) always applies the full transform.
 DEV Ray trav_ray(const DevObject& ob, const Ray& r0, float mbTime) {
     // the ray laundered, so the compiler does not hoist the transform's double conversions of
     // it out of the caller's object loop (twelve VGPRs live through every mesh walk, spilled at
@@ -1071,7 +1100,7 @@ DEV Ray trav_ray(const DevObject& ob, const Ray& r0, float mbTime) {
     asm volatile("" : "+v"(r.o.x), "+v"(r.o.y), "+v"(r.o.z), "+v"(r.d.x), "+v"(r.d.y), "+v"(r.d.z));
 #endif
     if (!(ob.flags & OBJF_IDENTITY)) return local_ray(ob, r, mbTime);
-    Ray lr = r;
+    Ray lr = ident_ray(r);
     if (ob.flags & OBJF_MOTION_BLUR) lr.o = add(lr.o, muls(ld3(ob.mbv), mbTime));
     return lr;
 }
@@ -1144,7 +1173,7 @@ DEV bool trace(const DevScene& S, Ray& r, float mbTime, float minT, float limit,
             }
         }
         // Mesh::Intersect (mesh.cpp:158-188); the mesh bbox test equals the root-node test
-        Ray lr = (FEAT & FEAT_XFORM) ? trav_ray(ob, r, mbTime) : r;
+        Ray lr = (FEAT & FEAT_XFORM) ? trav_ray(ob, r, mbTime) : ident_ray(r);
         int face = -1;
         float t = h.t;
         bool found;
@@ -1442,7 +1471,7 @@ DEV int trace_any_wide(const DevScene& S, const Ray& r, float minT0, float limit
                 continue;
             conf = box_hit_fast(ob.bmin[0], ob.bmin[1], ob.bmin[2], ob.bmax[0], ob.bmax[1], ob.bmax[2], r, rq, limit);
         }
-        const Ray lr = (FEAT & FEAT_XFORM) ? trav_ray(ob, r, 0.f) : r;
+        const Ray lr = (FEAT & FEAT_XFORM) ? trav_ray(ob, r, 0.f) : ident_ray(r);
         if (ob.aroot < 0) return -1;                 // no any-hit tree for this mesh: reference walk
         const int res = walk_wide_any_pk<STATS, DEFER>(S, ob.aroot, lr, minT0, limit, conf, c, ad);
         if (res > 0) return 1;

@@ -145,7 +145,7 @@ __global__ __launch_bounds__(256) void k_hitfix(const DevScene S, const DevCamer
             const float up = next_up(h.t);
             if (ob.kind == OBJ_INSTANCE)
                 sure &= box_hit(ob.bmin[0], ob.bmin[1], ob.bmin[2], ob.bmax[0], ob.bmax[1], ob.bmax[2], ray, up);
-            const Ray lr = (FEAT & FEAT_XFORM) ? trav_ray(ob, ray, mbTime) : ray;
+            const Ray lr = (FEAT & FEAT_XFORM) ? trav_ray(ob, ray, mbTime) : ident_ray(ray);
             const int leaf = S.face_leaf[f];
             const float4 a = S.nodes[2 * leaf], b = S.nodes[2 * leaf + 1];
             sure &= box_hit(a.x, a.y, a.z, a.w, b.x, b.y, lr, up);
@@ -207,7 +207,7 @@ DEV bool trace_wave(const DevScene& S, Ray& r, float mbTime, Hit& h) {
                 continue;
             }
         }
-        const Ray lr = (FEAT & FEAT_XFORM) ? trav_ray(ob, r, mbTime) : r;
+        const Ray lr = (FEAT & FEAT_XFORM) ? trav_ray(ob, r, mbTime) : ident_ray(r);
         const RayRcp q = ray_rcp(lr);
         float minT = h.t;
         int face = -1;

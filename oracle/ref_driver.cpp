@@ -29,6 +29,9 @@
 //       The reference's own Tonemapper::Tonemap (tonemapper.h:28-60) on an "RTGF" float
 //       image (as dump writes); writes "RTGL" int32 w, int32 h, w*h*3 uint8 (the LDR
 //       image main.cpp:187-195 saves for a tonemapped camera).
+//   refdriver rays <scene.xml> <rays.bin> <out.bin>
+//       Caller-supplied rays through the reference's own Shape::Intersect: the closest-hit and
+//       the shadow-ray object loops (rays_mode below); the edge-ray goldens.
 #define STB_IMAGE_WRITE_IMPLEMENTATION
 #include "stb_image_write.h"
 #define STB_IMAGE_IMPLEMENTATION
@@ -251,7 +254,95 @@ static int tonemap(const char* in, float key, float burn, float sat, float gamma
     return 0;
 }
 
+// Ray queries through the reference's own Shape::Intersect.  rays.bin: rtg_ray records (8 float32:
+// origin, tmax, direction, motion-blur time).  Two restated loops over the public scene lists:
+// IntersectObjects (raytracer.cpp:625-643) from hitInfo.minT = tmax, and CastShadowRay
+// (raytracer.cpp:585-623) from minT = lightSourceT = tmax with the emissive skip and time 0.
+// out.bin: "RTGQ" int32 n, then per ray int32 hasHit, the bits of minT, the position of hitShape
+// in the loop order (meshes, spheres, triangles; -1 for none) and the occlusion boolean.
+static int shape_position(const Scene& s, const Shape* p) {
+    if (!p) return -1;
+    int k = 0;
+    for (size_t i = 0; i < s.meshes.size(); ++i, ++k) if (s.meshes[i] == p) return k;
+    for (size_t i = 0; i < s.spheres.size(); ++i, ++k) if (s.spheres[i] == p) return k;
+    for (size_t i = 0; i < s.triangles.size(); ++i, ++k) if (s.triangles[i] == p) return k;
+    return -2;
+}
+
+static bool occluded(Scene& s, Ray& ray, float lightSourceT) {
+    for (size_t i = 0; i < s.meshes.size(); i++) {
+        Shape* mesh = s.meshes[i];
+        // (an InstancedMesh keeps its material in a member of its own, instancedMesh.hpp:23: the
+        // Shape::material_id that raytracer.cpp:590 reads is never written for it -- heap garbage
+        // that indexes out of range on some scenes -- so instances are taken as not emissive here,
+        // which is what every fixture's instances are)
+        if (!mesh->isInstance && s.materials[mesh->GetMaterial() - 1].type == Material::Emissive) continue;
+        mesh->Intersect(ray);
+        if (ray.hitInfo.hasHit && ray.hitInfo.minT < lightSourceT) return true;
+    }
+    for (size_t i = 0; i < s.spheres.size(); i++) {
+        s.spheres[i]->Intersect(ray);
+        if (ray.hitInfo.hasHit && ray.hitInfo.minT < lightSourceT) return true;
+    }
+    for (size_t i = 0; i < s.triangles.size(); i++) {
+        s.triangles[i]->Intersect(ray);
+        if (ray.hitInfo.hasHit && ray.hitInfo.minT < lightSourceT) return true;
+    }
+    return false;
+}
+
+static int rays_mode(const char* xml, const char* in, const char* out) {
+    Scene scene;
+    scene.loadFromXml(xml);
+    Raytracer renderer(scene);
+    Scene& s = renderer.scene;
+    FILE* f = std::fopen(in, "rb");
+    if (!f) { std::perror(in); return 1; }
+    std::vector<float> q;
+    float rec[8];
+    while (std::fread(rec, 4, 8, f) == 8) q.insert(q.end(), rec, rec + 8);
+    std::fclose(f);
+    const int32_t n = (int32_t)(q.size() / 8);
+    std::vector<int32_t> res((size_t)n * 4);
+    for (int32_t i = 0; i < n; ++i) {
+        const float* r = &q[(size_t)i * 8];
+        Ray ray;
+        ray.origin = Vec3f{r[0], r[1], r[2]};
+        ray.dir = Vec3f{r[4], r[5], r[6]};
+        ray.hitInfo.hasHit = false;
+        ray.hitInfo.minT = r[3];
+        ray.hitInfo.hitShape = nullptr;
+        ray.refractiveIndexOfCurrentMedium = 1.0f;
+        ray.motionBlurTime = r[7];
+        for (size_t k = 0; k < s.meshes.size(); k++) s.meshes[k]->Intersect(ray);
+        for (size_t k = 0; k < s.spheres.size(); k++) s.spheres[k]->Intersect(ray);
+        for (size_t k = 0; k < s.triangles.size(); k++) s.triangles[k]->Intersect(ray);
+        uint32_t bits;
+        std::memcpy(&bits, &ray.hitInfo.minT, 4);
+        res[(size_t)i * 4] = ray.hitInfo.hasHit ? 1 : 0;
+        res[(size_t)i * 4 + 1] = (int32_t)bits;
+        res[(size_t)i * 4 + 2] = shape_position(s, ray.hitInfo.hasHit ? ray.hitInfo.hitShape : nullptr);
+        Ray sh;
+        sh.origin = Vec3f{r[0], r[1], r[2]};
+        sh.dir = Vec3f{r[4], r[5], r[6]};
+        sh.hitInfo.hasHit = false;
+        sh.hitInfo.minT = r[3];
+        sh.hitInfo.hitShape = nullptr;
+        sh.refractiveIndexOfCurrentMedium = 1.0f;
+        sh.motionBlurTime = 0.0f;
+        res[(size_t)i * 4 + 3] = occluded(s, sh, r[3]) ? 1 : 0;
+    }
+    f = std::fopen(out, "wb");
+    if (!f) { std::perror(out); return 1; }
+    std::fwrite("RTGQ", 1, 4, f);
+    std::fwrite(&n, 4, 1, f);
+    std::fwrite(res.data(), 4, res.size(), f);
+    std::fclose(f);
+    return 0;
+}
+
 int main(int argc, char** argv) {
+    if (argc >= 5 && !std::strcmp(argv[1], "rays")) return rays_mode(argv[2], argv[3], argv[4]);
     if (argc >= 8 && !std::strcmp(argv[1], "tonemap"))
         return tonemap(argv[2], std::atof(argv[3]), std::atof(argv[4]), std::atof(argv[5]), std::atof(argv[6]), argv[7]);
     if (argc >= 4 && !std::strcmp(argv[1], "dump")) return dump(argv[2], argv[3], argc > 4 ? std::atoi(argv[4]) : 0);

@@ -8,7 +8,10 @@ tests/golden/<name>.npz plus tests/golden/manifest.json (sizes, kinds, SHA-256).
 Fixture scenes live in tests/golden/scenes/: copies of the reference's own scene files
 (archive/hw1_inputs, data) re-sized, plus scenes authored in its XML schema.
 
-    python tests/golden/make_goldens.py            # regenerate everything
+    python tests/golden/make_goldens.py            # regenerate everything (the edge-ray goldens
+                                                   # last: they need the built librtgpu.so)
+    python tests/golden/make_goldens.py edge_rays  # only the edge-ray goldens (edge_rays_<scene>.npz)
+                                                   # and scenes/edge_lattice.xml
 """
 import hashlib
 import json
@@ -763,11 +766,235 @@ def make_stoch_avg(names):
     return man
 
 
+# Edge-ray goldens (edge_rays_<scene>.npz): the rays of tests/edge_rays.py through the reference's
+# own Shape::Intersect (refdriver rays), closest hit and occlusion.
+EDGE_SCENES = ("simple", "spheres", "transforms_textures", "cornell_dielectric", "mesh_light", "dof_motion",
+               "edge_lattice", "edge_roof")
+
+
+def make_edge_lattice():
+    """Dyadic geometry for the exact checks: two stacked 8x8 lattices of unit squares at integer
+    coordinates, each square cut in two -- mesh 1 in the plane z = 1 over [-4, 4]^2, mesh 2 in
+    z = -2 over [-9, -1]^2 (entirely negative: its boxes carry the FLT_MIN maxima) --, an instance
+    of mesh 1 under a pure translation and a sphere at an integer centre."""
+    verts, meshes = [], []
+    for x0, y0, z in ((-4, -4, 1), (-9, -9, -2)):
+        base = len(verts)
+        verts += [(x0 + i, y0 + j, z) for j in range(9) for i in range(9)]
+        tri = []
+        for j in range(8):
+            for i in range(8):
+                a, b, c, d = (base + 1 + i + 9 * j, base + 2 + i + 9 * j, base + 2 + i + 9 * (j + 1),
+                              base + 1 + i + 9 * (j + 1))
+                tri += [f"{a} {b} {c}", f"{a} {c} {d}"]
+        meshes.append(tri)
+    verts.append((-6, 3, 3))
+    vdata = "\n        ".join("%d %d %d" % v for v in verts)
+    f1, f2 = ("\n                ".join(m) for m in meshes)
+    xml = f"""<Scene>
+    <MaxRecursionDepth>1</MaxRecursionDepth>
+    <BackgroundColor>0 0 0</BackgroundColor>
+    <ShadowRayEpsilon>1e-3</ShadowRayEpsilon>
+    <Cameras>
+        <Camera id="1">
+            <Position>-2 -1 16</Position>
+            <Gaze>0 0 -1</Gaze>
+            <Up>0 1 0</Up>
+            <NearPlane>-1 1 -0.75 0.75</NearPlane>
+            <NearDistance>1</NearDistance>
+            <ImageResolution>64 48</ImageResolution>
+            <ImageName>edge_lattice.png</ImageName>
+        </Camera>
+    </Cameras>
+    <Lights>
+        <AmbientLight>25 25 25</AmbientLight>
+        <PointLight id="1"><Position>0 0 12</Position><Intensity>1000 1000 1000</Intensity></PointLight>
+    </Lights>
+    <Materials>
+        <Material id="1">
+            <AmbientReflectance>1 1 1</AmbientReflectance>
+            <DiffuseReflectance>1 1 1</DiffuseReflectance>
+            <SpecularReflectance>0 0 0</SpecularReflectance>
+            <PhongExponent>1</PhongExponent>
+        </Material>
+    </Materials>
+    <VertexData>
+        {vdata}
+    </VertexData>
+    <Transformations>
+        <Translation id="1">3 -2 4</Translation>
+    </Transformations>
+    <Objects>
+        <Mesh id="1">
+            <Material>1</Material>
+            <Faces>
+                {f1}
+            </Faces>
+        </Mesh>
+        <Mesh id="2">
+            <Material>1</Material>
+            <Faces>
+                {f2}
+            </Faces>
+        </Mesh>
+        <MeshInstance id="3" baseMeshId="1">
+            <Material>1</Material>
+            <Transformations>t1</Transformations>
+        </MeshInstance>
+        <Sphere id="1">
+            <Material>1</Material>
+            <Center>{len(verts)}</Center>
+            <Radius>1</Radius>
+        </Sphere>
+    </Objects>
+</Scene>
+"""
+    with open(os.path.join(SCENES, "edge_lattice.xml"), "w") as f:
+        f.write(xml)
+
+
+def make_edge_roof():
+    """What edge_lattice cannot have: boxes with thickness on every axis around slanted faces.  A flat
+    box is never "sure" in the fused slab test (tmax - tmin is 0), so the lattice's rays always take
+    the exact branch under an instance; here an 8x8 height field over [-4, 4]^2 with integer heights
+    0..3 -- leaf and inner boxes with planes at integer coordinates, 0 among them -- and an instance
+    of it under the translation (3, 2, 4), whose inverse's last column is negative on all three
+    axes, so that a -0 direction component survives the product into the instance's frame."""
+    verts = [(i - 4, j - 4, (3 * i + 5 * j) % 4) for j in range(9) for i in range(9)]
+    tri = []
+    for j in range(8):
+        for i in range(8):
+            a, b, c, d = 1 + i + 9 * j, 2 + i + 9 * j, 2 + i + 9 * (j + 1), 1 + i + 9 * (j + 1)
+            tri += [f"{a} {b} {c}", f"{a} {c} {d}"]
+    vdata = "\n        ".join("%d %d %d" % v for v in verts)
+    faces = "\n                ".join(tri)
+    xml = f"""<Scene>
+    <MaxRecursionDepth>1</MaxRecursionDepth>
+    <BackgroundColor>0 0 0</BackgroundColor>
+    <ShadowRayEpsilon>1e-3</ShadowRayEpsilon>
+    <Cameras>
+        <Camera id="1">
+            <Position>1 1 20</Position>
+            <Gaze>0 0 -1</Gaze>
+            <Up>0 1 0</Up>
+            <NearPlane>-1 1 -0.75 0.75</NearPlane>
+            <NearDistance>1.5</NearDistance>
+            <ImageResolution>64 48</ImageResolution>
+            <ImageName>edge_roof.png</ImageName>
+        </Camera>
+    </Cameras>
+    <Lights>
+        <AmbientLight>25 25 25</AmbientLight>
+        <PointLight id="1"><Position>0 0 15</Position><Intensity>1000 1000 1000</Intensity></PointLight>
+    </Lights>
+    <Materials>
+        <Material id="1">
+            <AmbientReflectance>1 1 1</AmbientReflectance>
+            <DiffuseReflectance>1 1 1</DiffuseReflectance>
+            <SpecularReflectance>0 0 0</SpecularReflectance>
+            <PhongExponent>1</PhongExponent>
+        </Material>
+    </Materials>
+    <VertexData>
+        {vdata}
+    </VertexData>
+    <Transformations>
+        <Translation id="1">3 2 4</Translation>
+    </Transformations>
+    <Objects>
+        <Mesh id="1">
+            <Material>1</Material>
+            <Faces>
+                {faces}
+            </Faces>
+        </Mesh>
+        <MeshInstance id="2" baseMeshId="1">
+            <Material>1</Material>
+            <Transformations>t1</Transformations>
+        </MeshInstance>
+    </Objects>
+</Scene>
+"""
+    with open(os.path.join(SCENES, "edge_roof.xml"), "w") as f:
+        f.write(xml)
+
+
+def run_ref_rays(name, rays):
+    """refdriver rays on scenes/<name>.xml: (hasHit, minT bits, loop position, occluded) int32
+    (n, 4), or None when the reference does not return."""
+    src, dst = os.path.join(HERE, "_rays_in.bin"), os.path.join(HERE, "_rays_out.bin")
+    rays.tofile(src)
+    try:
+        rc = subprocess.run([DRIVER, "rays", name + ".xml", src, dst], cwd=SCENES, stdout=subprocess.DEVNULL,
+                            timeout=600).returncode
+        if rc != 0:
+            return None
+        raw = open(dst, "rb").read()
+    except subprocess.TimeoutExpired:
+        return None
+    finally:
+        for p in (src, dst):
+            if os.path.exists(p):
+                os.remove(p)
+    assert raw[:4] == b"RTGQ" and np.frombuffer(raw[4:8], np.int32)[0] == rays.size
+    return np.frombuffer(raw[8:], np.int32).reshape(-1, 4).copy()
+
+
+def make_edge_rays(names):
+    """Generate the edge rays of each scene (tests/edge_rays.py on our own description of it), run
+    the reference on them twice, and store rays, class labels and the reference's answers.  A class
+    whose answers differ between the two runs is dropped and named; class G (non-finite rays) is
+    stored only if the reference returns on it."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import edge_rays
+    import query_util
+    import rtgpu
+    make_edge_lattice()
+    make_edge_roof()
+    for name in names:
+        old = os.getcwd()
+        os.chdir(SCENES)
+        try:
+            hs = rtgpu.HostScene(name + ".xml")
+            # refdriver's shadow loop takes instances as not emissive (it cannot read their material):
+            # its answers are the reference's only while no instance is
+            objs = query_util.scene_arrays(hs)[1]
+            inst = objs["kind"] == query_util.RTG_OBJ_INSTANCE
+            assert not np.any(objs["flags"][inst] & query_util.RTG_OBJF_SHADOW_SKIP), (name, "emissive instance")
+            rays, labels = edge_rays.generate(hs)
+        finally:
+            os.chdir(old)
+        g = labels == edge_rays.CLASSES["G"]
+        ans = np.zeros((rays.size, 4), np.int32)
+        keep = np.ones(rays.size, bool)
+        dropped = []
+        for part in (~g, g):
+            a, b = run_ref_rays(name, rays[part]), run_ref_rays(name, rays[part])
+            if a is None or b is None:
+                assert part is g, (name, "the reference failed on finite rays")
+                keep &= ~part
+                dropped.append("G (no return)")
+                continue
+            ans[part] = a
+            for c in np.unique(labels[part]):
+                sel = labels[part] == c
+                if not np.array_equal(a[sel], b[sel]):
+                    keep &= labels != c
+                    dropped.append(edge_rays.NAMES[int(c)] + " (two runs differ)")
+        np.savez_compressed(os.path.join(HERE, f"edge_rays_{name}.npz"), rays=rays[keep], labels=labels[keep],
+                            has_hit=ans[keep, 0].astype(np.int8), t_bits=ans[keep, 1].view(np.uint32),
+                            position=ans[keep, 2], occluded=ans[keep, 3].astype(np.int8))
+        print("edge rays", name, int(keep.sum()), "dropped:", dropped or "none")
+
+
 def main():
     if not os.path.exists(DRIVER):
         sys.exit(f"{DRIVER} missing: build it with `make -C {os.path.join(ROOT, 'oracle')}` (needs /root/reference)")
     man = {}
     only = set(sys.argv[1:])
+    if only and only <= {"edge_rays"} | {"edge_rays_" + n for n in EDGE_SCENES}:
+        make_edge_rays(EDGE_SCENES if "edge_rays" in only else [o[len("edge_rays_"):] for o in sorted(only)])
+        return
     if only == {"tonemap"}:
         make_tonemap_goldens()
         return
@@ -805,6 +1032,8 @@ def main():
         man = old
     with open(path, "w") as f:
         json.dump(man, f, indent=1, sort_keys=True)
+    if not only:
+        make_edge_rays(EDGE_SCENES)
 
 
 if __name__ == "__main__":
