@@ -192,6 +192,35 @@ public:
         return V((float)S.background[0], (float)S.background[1], (float)S.background[2]);
     }
 
+    // Radiance queries: PerPixel below a ray of the caller's.  The ray is taken
+    // as given -- medium 1, minT = tmax --, `eye` is the viewer of a primary hit, and a miss follows
+    // PerPixel's branches with (coordX, coordY) the pixel of the background-texture lookup.  *t
+    // receives the primary ray's accepted distance (tmax on a miss).
+    Vec3f PerRay(Vec3f origin, Vec3f dir, float tmax, float time, Vec3f eye, int coordX, int coordY, uint64_t key,
+                 float* t) {
+        Ray ray;
+        ray.origin = origin;
+        ray.dir = dir;
+        ray.hitInfo.hasHit = false;
+        ray.hitInfo.minT = tmax;
+        ray.refractiveIndexOfCurrentMedium = 1.0f;
+        ray.motionBlurTime = time;
+        ray.key = key;
+        cnt.camera++;
+        IntersectObjects(ray);
+        *t = ray.hitInfo.minT;
+        if (ray.hitInfo.hasHit) {
+            return PerformShading(ray, eye, S.max_recursion_depth);
+        } else if (S.bg_texture >= 0) {
+            float u = coordX / (float)cam.width;
+            float v = coordY / (float)cam.height;
+            return TexRGB(S.textures[S.bg_texture], u, v);
+        } else if (S.num_env_lights > 0) {
+            return EnvSample(0, ray.dir);
+        }
+        return V((float)S.background[0], (float)S.background[1], (float)S.background[2]);
+    }
+
 private:
     const rtg_scene_desc& S;
     const rtg_camera& cam;
@@ -1200,6 +1229,64 @@ int oracle_render_pixel(const rtg_scene_desc* desc, int camera, int x, int y, ui
     PixelValue(tr, x, y, cam.width, cam.spp < 1 ? 1 : cam.spp, seed, 0, cam.spp < 1 ? 1 : cam.spp, nullptr, c);
     rgb[0] = c.x; rgb[1] = c.y; rgb[2] = c.z;
     if (n_near) *n_near = (int32_t)tr.env_near.size();
+    return 0;
+}
+
+// Radiance queries as INTEGRATION.md §6 states them, restated here without any device or product
+// code: ray i (an rtg_ray record) plays pixel p = pixel_ids ? pixel_ids[i] : first_pixel + i of
+// camera `camera`; sample s of it runs Tracer::PerRay under root_key(seed, p, s).  camera_eye != 0:
+// primary hits are seen from the camera's position, else from the ray's origin.  rgbt (4 floats
+// per ray): one sample's colour, or (((0 + c_0) + c_1) + ...) / (float)sample_count in float, and
+// the primary ray's t (tmax on a miss).  env_eps / env_flip: as oracle_render_pixel, applied to
+// every ray alike; n_near (nullable, one int32 per ray) receives the number of distinct
+// environment lookups of the ray's samples within env_eps of a texel boundary.
+int oracle_radiance_rays(const rtg_scene_desc* desc, int camera, int sample_begin, int sample_count, int camera_eye,
+                         uint64_t seed, int first_pixel, const rtg_ray* rays, const int32_t* pixel_ids, int64_t n,
+                         float env_eps, uint64_t env_flip, int threads, float* rgbt, int32_t* n_near) {
+    if (!desc || camera < 0 || camera >= desc->num_cameras || n < 0 || (n > 0 && (!rays || !rgbt))) return -1;
+    if (desc->num_faces > 0 && desc->num_nodes == 0) return -2;
+    const rtg_camera& cam = desc->cameras[camera];
+    if (sample_begin < 0) sample_begin = 0;
+    if (sample_count < 1) sample_count = 1;
+    if (threads < 1) threads = 1;
+    auto work = [&](int t0) {
+        Counters cnt;
+        Tracer tr(*desc, cam, cnt);
+        tr.env_eps = env_eps;
+        tr.env_flip = env_flip;
+        for (int64_t i = t0; i < n; i += threads) {
+            const rtg_ray& r = rays[i];
+            const int p = pixel_ids ? pixel_ids[i] : first_pixel + (int)i;
+            const int py = p / cam.width, px = p - py * cam.width;
+            const Vec3f o = V(r.ox, r.oy, r.oz), d = V(r.dx, r.dy, r.dz);
+            const Vec3f eye = camera_eye ? V(cam.position) : o;
+            tr.env_near.clear();
+            float t = r.tmax;
+            Vec3f color;
+            if (sample_count == 1) {
+                color = tr.PerRay(o, d, r.tmax, r.time, eye, px, py, root_key(seed, p, sample_begin), &t);
+            } else {
+                Vec3f acc = V(0, 0, 0);
+                for (int s = sample_begin; s < sample_begin + sample_count; ++s) {
+                    const Vec3f c = tr.PerRay(o, d, r.tmax, r.time, eye, px, py, root_key(seed, p, s), &t);
+                    acc.x += c.x;
+                    acc.y += c.y;
+                    acc.z += c.z;
+                }
+                const float k = (float)sample_count;
+                color = V(acc.x / k, acc.y / k, acc.z / k);
+            }
+            float* out = rgbt + 4 * i;
+            out[0] = color.x; out[1] = color.y; out[2] = color.z; out[3] = t;
+            if (n_near) n_near[i] = (int32_t)tr.env_near.size();
+        }
+    };
+    if (threads == 1) work(0);
+    else {
+        std::vector<std::thread> th;
+        for (int t = 0; t < threads; ++t) th.emplace_back(work, t);
+        for (auto& t : th) t.join();
+    }
     return 0;
 }
 

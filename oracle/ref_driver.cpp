@@ -32,6 +32,10 @@
 //   refdriver rays <scene.xml> <rays.bin> <out.bin>
 //       Caller-supplied rays through the reference's own Shape::Intersect: the closest-hit and
 //       the shadow-ray object loops (rays_mode below); the edge-ray goldens.
+//   refdriver radiance <scene.xml> <rays.bin> <out.bin> [camera]
+//       Caller-supplied rays through the reference's own IntersectObjects / PerformShading
+//       (radiance_mode below); the radiance-ray goldens.  This translation unit alone is compiled
+//       with -fno-access-control (oracle/Makefile) so that it can call those private members.
 #define STB_IMAGE_WRITE_IMPLEMENTATION
 #include "stb_image_write.h"
 #define STB_IMAGE_IMPLEMENTATION
@@ -51,6 +55,7 @@
 #undef STB_IMAGE_IMPLEMENTATION          // emitted once above (raytracer.hpp -> image.h)
 #include "LDRImage.h"
 #include "gaussian.h"
+#include "instancedMesh.hpp"
 
 using namespace DorkTracer;
 
@@ -341,7 +346,80 @@ static int rays_mode(const char* xml, const char* in, const char* out) {
     return 0;
 }
 
+// Radiance of caller-supplied rays: PerPixel (raytracer.cpp:38-63) below a given ray instead of
+// GenerateRay's.  rays.bin: "RTGR" int32 n, int32 eye (0: the ray's origin, 1: the camera's
+// position), n rtg_ray records (8 float32: origin, tmax, direction, motion-blur time), n int32 pixel
+// ids.  Per ray: GenerateRay(0, 0, cam) -- so that every field the reference initialises is
+// initialised --, then origin, direction, hitInfo.minT = tmax, hasHit = false and motionBlurTime
+// overwritten; IntersectObjects; on a hit PerformShading(ray, eye, max_recursion_depth), on a miss
+// PerPixel's three branches with (px, py) = (id % width, id / width).  out.bin: "RTGC" int32 n,
+// then per ray the bits of r, g, b and of hitInfo.minT (tmax's own bits on a miss).
+static int radiance_mode(const char* xml, const char* in, const char* out, int ci) {
+    Scene scene;
+    scene.loadFromXml(xml);
+    Raytracer renderer(scene);
+    if (ci < 0 || ci >= (int)scene.cameras.size()) { std::fprintf(stderr, "bad camera\n"); return 2; }
+    Camera& cam = scene.cameras[ci];
+    if (cam.IsPathTracingEnabled()) renderer.EnablePathTracing(cam.GetRendererParams());
+    renderer.activeCamera = &cam;
+    Scene& s = renderer.scene;
+    // CastShadowRay reads Shape::material_id of every mesh (raytracer.cpp:590), which an
+    // InstancedMesh never writes (its SetMaterial sets a member of its own, instancedMesh.hpp:22):
+    // heap garbage that indexes out of range on some scenes (edge_roof segfaults).  Give it the
+    // instance's own material, so that the read is defined: an instance then occludes unless its
+    // material is emissive -- what any in-range garbage gives on fixtures without emissive materials.
+    for (size_t k = 0; k < s.meshes.size(); k++)
+        if (s.meshes[k]->isInstance)
+            static_cast<Shape*>(s.meshes[k])->material_id = static_cast<InstancedMesh*>(s.meshes[k])->material_id;
+    FILE* f = std::fopen(in, "rb");
+    if (!f) { std::perror(in); return 1; }
+    char magic[4];
+    int32_t hd[2];
+    if (std::fread(magic, 1, 4, f) != 4 || std::memcmp(magic, "RTGR", 4) || std::fread(hd, 4, 2, f) != 2 || hd[0] < 0) return 1;
+    const int32_t n = hd[0];
+    std::vector<float> q((size_t)n * 8);
+    std::vector<int32_t> ids(n);
+    if (std::fread(q.data(), 4, q.size(), f) != q.size() || std::fread(ids.data(), 4, ids.size(), f) != ids.size()) return 1;
+    std::fclose(f);
+    std::vector<uint32_t> res((size_t)n * 4);
+    for (int32_t i = 0; i < n; ++i) {
+        const float* r = &q[(size_t)i * 8];
+        Ray ray = renderer.GenerateRay(0, 0, cam);
+        ray.origin = Vec3f{r[0], r[1], r[2]};
+        ray.dir = Vec3f{r[4], r[5], r[6]};
+        ray.hitInfo.hasHit = false;
+        ray.hitInfo.minT = r[3];
+        ray.motionBlurTime = r[7];
+        renderer.IntersectObjects(ray);
+        Vec3f c;
+        if (ray.hitInfo.hasHit) {
+            Vec3f eye = hd[1] ? cam.position : ray.origin;
+            c = renderer.PerformShading(ray, eye, s.max_recursion_depth);
+        } else if (s.bgTexture != nullptr) {
+            const int px = ids[i] % cam.imageWidth, py = ids[i] / cam.imageWidth;
+            float u = px / (float)cam.imageWidth;
+            float v = py / (float)cam.imageHeight;
+            c = s.bgTexture->GetRGBSample(u, v);
+        } else if (s.sphericalEnvLights.size() > 0) {
+            c = s.sphericalEnvLights[0]->GetSample(ray.dir);
+        } else {
+            c = Vec3f(s.background_color.x, s.background_color.y, s.background_color.z);
+        }
+        const float v4[4] = {c.x, c.y, c.z, ray.hitInfo.minT};
+        std::memcpy(&res[(size_t)i * 4], v4, 16);
+    }
+    f = std::fopen(out, "wb");
+    if (!f) { std::perror(out); return 1; }
+    std::fwrite("RTGC", 1, 4, f);
+    std::fwrite(&n, 4, 1, f);
+    std::fwrite(res.data(), 4, res.size(), f);
+    std::fclose(f);
+    return 0;
+}
+
 int main(int argc, char** argv) {
+    if (argc >= 5 && !std::strcmp(argv[1], "radiance"))
+        return radiance_mode(argv[2], argv[3], argv[4], argc > 5 ? std::atoi(argv[5]) : 0);
     if (argc >= 5 && !std::strcmp(argv[1], "rays")) return rays_mode(argv[2], argv[3], argv[4]);
     if (argc >= 8 && !std::strcmp(argv[1], "tonemap"))
         return tonemap(argv[2], std::atof(argv[3]), std::atof(argv[4]), std::atof(argv[5]), std::atof(argv[6]), argv[7]);

@@ -12,6 +12,8 @@ Fixture scenes live in tests/golden/scenes/: copies of the reference's own scene
                                                    # last: they need the built librtgpu.so)
     python tests/golden/make_goldens.py edge_rays  # only the edge-ray goldens (edge_rays_<scene>.npz)
                                                    # and scenes/edge_lattice.xml
+    python tests/golden/make_goldens.py radiance_rays   # only the radiance-ray goldens
+                                                        # (radiance_rays_<scene>.npz)
 """
 import hashlib
 import json
@@ -987,11 +989,80 @@ def make_edge_rays(names):
         print("edge rays", name, int(keep.sum()), "dropped:", dropped or "none")
 
 
+# Radiance-ray goldens (radiance_rays_<scene>.npz): the off-camera rays of tests/radiance_rays.py
+# through the reference's own IntersectObjects / PerformShading (refdriver radiance), under both
+# eyes.  The scenes whose render golden is `exact` and that between them cover the shading, and
+# edge_roof for its instance.
+RADIANCE_SCENES = ("simple", "spheres_mirror", "cornell_dielectric", "cornell_conductors", "brdf_lights", "image_tex",
+                   "transforms_textures", "bump_normal", "scienceTree_diamond", "edge_roof")
+RADIANCE_MAX_DROP = 0.01          # of a scene's rays; and no whole class
+RADIANCE_MAX_BYTES = 64 * 1024
+
+
+def run_ref_radiance(name, rays, ids, camera_eye):
+    """refdriver radiance on scenes/<name>.xml: (n, 4) uint32 -- the bits of r, g, b and minT."""
+    src, dst = os.path.join(HERE, "_rad_in.bin"), os.path.join(HERE, "_rad_out.bin")
+    with open(src, "wb") as f:
+        f.write(b"RTGR" + np.array([rays.size, int(camera_eye)], np.int32).tobytes() + rays.tobytes()
+                + np.ascontiguousarray(ids, np.int32).tobytes())
+    try:
+        subprocess.run([DRIVER, "radiance", name + ".xml", src, dst], cwd=SCENES, check=True, stdout=subprocess.DEVNULL,
+                       timeout=600)
+        raw = open(dst, "rb").read()
+    finally:
+        for p in (src, dst):
+            if os.path.exists(p):
+                os.remove(p)
+    assert raw[:4] == b"RTGC" and np.frombuffer(raw[4:8], np.int32)[0] == rays.size
+    return np.frombuffer(raw[8:], np.uint32).reshape(-1, 4).copy()
+
+
+def make_radiance_rays(names):
+    """Generate each scene's rays (tests/radiance_rays.py on our own description of it), run the
+    reference on them twice per eye (it reads an uninitialised material id for instances in
+    CastShadowRay: see occluded() in ref_driver.cpp), drop the rays on which two runs differ -- a NaN
+    equal to a NaN whatever its payload -- and store rays, ids, labels and the reference's colours:
+    rgb_origin / rgb_camera (uint32 bits, eye = the ray's origin / the camera's position), t_bits
+    (the same under both eyes), dropped (per class, in radiance_rays.CLASSES order)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import radiance_rays as rr
+    import rtgpu
+    make_edge_roof()
+    for name in names:
+        old = os.getcwd()
+        os.chdir(SCENES)
+        try:
+            rays, ids, labels = rr.generate(rtgpu.HostScene(name + ".xml"))
+        finally:
+            os.chdir(old)
+
+        def same(a, b):
+            fa, fb = a.view(np.float32), b.view(np.float32)
+            return ((a == b) | (np.isnan(fa) & np.isnan(fb))).all(1)
+
+        runs = [[run_ref_radiance(name, rays, ids, eye) for _ in range(2)] for eye in (False, True)]
+        keep = same(*runs[0]) & same(*runs[1]) & same(runs[0][0][:, 3:], runs[1][0][:, 3:])
+        dropped = np.array([int((~keep & (labels == c)).sum()) for c in sorted(rr.NAMES)], np.int32)
+        for c in sorted(rr.NAMES):
+            assert not np.any(labels == c) or np.any(keep & (labels == c)), (name, "class lost", rr.NAMES[c])
+        assert (~keep).sum() <= RADIANCE_MAX_DROP * rays.size, (name, "dropped", dropped)
+        path = os.path.join(HERE, f"radiance_rays_{name}.npz")
+        np.savez_compressed(path, rays=rays[keep], ids=ids[keep], labels=labels[keep],
+                            rgb_origin=runs[0][0][keep, :3], rgb_camera=runs[1][0][keep, :3],
+                            t_bits=runs[0][0][keep, 3], dropped=dropped)
+        size = os.path.getsize(path)
+        assert size <= RADIANCE_MAX_BYTES, (name, size)
+        print("radiance rays", name, int(keep.sum()), "dropped per class", dropped.tolist(), "bytes", size)
+
+
 def main():
     if not os.path.exists(DRIVER):
         sys.exit(f"{DRIVER} missing: build it with `make -C {os.path.join(ROOT, 'oracle')}` (needs /root/reference)")
     man = {}
     only = set(sys.argv[1:])
+    if only and only <= {"radiance_rays"} | {"radiance_rays_" + n for n in RADIANCE_SCENES}:
+        make_radiance_rays(RADIANCE_SCENES if "radiance_rays" in only else [o[len("radiance_rays_"):] for o in sorted(only)])
+        return
     if only and only <= {"edge_rays"} | {"edge_rays_" + n for n in EDGE_SCENES}:
         make_edge_rays(EDGE_SCENES if "edge_rays" in only else [o[len("edge_rays_"):] for o in sorted(only)])
         return
@@ -1034,6 +1105,7 @@ def main():
         json.dump(man, f, indent=1, sort_keys=True)
     if not only:
         make_edge_rays(EDGE_SCENES)
+        make_radiance_rays(RADIANCE_SCENES)
 
 
 if __name__ == "__main__":

@@ -75,6 +75,31 @@ def render_pixel(host_scene, x, y, camera=0, seed=0x5EED, env_eps=0.0, env_flip=
     return rgb, n.value
 
 
+def radiance(host_scene, rays, pixel_ids=None, camera=0, sample=0, samples=1, seed=0x5EED, first_pixel=0,
+             camera_eye=False, env_eps=0.0, env_flip=0, threads=None):
+    """CPU restatement of a radiance query (oracle_radiance_rays), the arguments
+    of rtgpu.DeviceScene.radiance -> ((n, 4) float32 rgb + primary t, n_near int32 per ray).
+    rays: RAY_DTYPE-compatible 32-byte records.  env_eps / env_flip: as render_pixel."""
+    L = lib()
+    vp = ctypes.c_void_p
+    L.oracle_radiance_rays.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint64,
+                                       ctypes.c_int, vp, vp, ctypes.c_int64, ctypes.c_float, ctypes.c_uint64,
+                                       ctypes.c_int, vp, vp]
+    rays = np.ascontiguousarray(rays)
+    assert rays.dtype.itemsize == 32 and rays.ndim == 1
+    n = rays.size
+    ids = None if pixel_ids is None else np.ascontiguousarray(pixel_ids, np.int32)
+    assert ids is None or ids.size == n
+    out = np.zeros((n, 4), np.float32)
+    near = np.zeros(n, np.int32)
+    threads = threads or min(16, os.cpu_count() or 1)
+    if L.oracle_radiance_rays(host_scene.desc, camera, sample, samples, int(bool(camera_eye)), seed, first_pixel,
+                              rays.ctypes.data, None if ids is None else ids.ctypes.data, n, env_eps, env_flip,
+                              threads, out.ctypes.data, near.ctypes.data):
+        raise RuntimeError("oracle_radiance_rays failed")
+    return out, near
+
+
 def explain_env_flips(host_scene, got, ref, rows=(0, 0), camera=0, seed=0x5EED, env_eps=2e-3, rel=1e-4):
     """Every pixel of `got` (GPU, rows [rows[0], ...) of the frame) outside the parity bound of
     `ref` (oracle), explained: some set of environment lookups within env_eps of a texel
