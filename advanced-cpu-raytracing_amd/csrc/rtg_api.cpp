@@ -15,10 +15,10 @@
 #include "host_assets.hpp"
 #include "host_query.hpp"
 #include "host_scene.hpp"
-#include "rtg_ahb.hpp"
 #include "rtg_device.hpp"
 #include "rtg_kernels.hpp"
 #include "rtgpu.h"
+#include "scene_tables.hpp"
 
 namespace {
 
@@ -40,24 +40,6 @@ int set_err(int code, const char* fmt, ...) {
         if (e_ != hipSuccess) return set_err(RTG_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 
-// Ken Perlin's reference permutation ("Improving Noise", SIGGRAPH 2002), duplicated to
-// 512 entries, and the 12 cube-edge gradients -- the tables perlinTexture.cpp:5-37 uses.
-const int kPerm256[256] = {
-    151, 160, 137, 91,  90,  15,  131, 13,  201, 95,  96,  53,  194, 233, 7,   225, 140, 36,  103, 30,  69,  142,
-    8,   99,  37,  240, 21,  10,  23,  190, 6,   148, 247, 120, 234, 75,  0,   26,  197, 62,  94,  252, 219, 203,
-    117, 35,  11,  32,  57,  177, 33,  88,  237, 149, 56,  87,  174, 20,  125, 136, 171, 168, 68,  175, 74,  165,
-    71,  134, 139, 48,  27,  166, 77,  146, 158, 231, 83,  111, 229, 122, 60,  211, 133, 230, 220, 105, 92,  41,
-    55,  46,  245, 40,  244, 102, 143, 54,  65,  25,  63,  161, 1,   216, 80,  73,  209, 76,  132, 187, 208, 89,
-    18,  169, 200, 196, 135, 130, 116, 188, 159, 86,  164, 100, 109, 198, 173, 186, 3,   64,  52,  217, 226, 250,
-    124, 123, 5,   202, 38,  147, 118, 126, 255, 82,  85,  212, 207, 206, 59,  227, 47,  16,  58,  17,  182, 189,
-    28,  42,  223, 183, 170, 213, 119, 248, 152, 2,   44,  154, 163, 70,  221, 153, 101, 155, 167, 43,  172, 9,
-    129, 22,  39,  253, 19,  98,  108, 110, 79,  113, 224, 232, 178, 185, 112, 104, 218, 246, 97,  228, 251, 34,
-    242, 193, 238, 210, 144, 12,  191, 179, 162, 241, 81,  51,  145, 235, 249, 14,  239, 107, 49,  192, 214, 31,
-    181, 199, 106, 157, 184, 84,  204, 176, 115, 121, 50,  45,  127, 4,   150, 254, 138, 236, 205, 93,  222, 114,
-    67,  29,  24,  72,  243, 141, 128, 195, 78,  66,  215, 61,  156, 180};
-const float kGrad[36] = {1, 1, 0, -1, 1, 0, 1, -1, 0, -1, -1, 0, 1, 0, 1, -1, 0, 1,
-                         1, 0, -1, -1, 0, -1, 0, 1, 1, 0, -1, 1, 0, 1, -1, 0, -1, -1};
-
 template <typename T>
 struct DevBuf {
     T* p = nullptr;
@@ -77,8 +59,6 @@ struct DevBuf {
         return hipMemcpy(p, v.data(), n * sizeof(T), hipMemcpyHostToDevice);
     }
 };
-
-void f4(float* dst, const rtg_float3& v, float w = 0.f) { dst[0] = v.x; dst[1] = v.y; dst[2] = v.z; dst[3] = w; }
 
 }  // namespace
 
@@ -267,11 +247,12 @@ int rtg_device_count(int32_t* count) {
 }
 
 // Device ingest: every mesh's BVH and face order built on the GPU (rtg_bvh.hip) straight
-// into the scene's walk buffers; facePerm receives the final order (mesh lights sample it).
-static int build_bvh_on_device(rtg_scene* sc, const rtg_scene_desc* d, bool anyUV, bool anyMapped,
-                               std::vector<int>& meshBegin, std::vector<int>& meshEnd, bool& bigleaf,
-                               std::vector<int>& facePerm) {
+// into the scene's walk buffers; rb receives the node ranges and the final face order (mesh
+// lights sample it) and, with `records`, host copies of the walk records (the any-hit trees
+// are built from them).
+static int build_bvh_on_device(rtg_scene* sc, const rtg_scene_desc* d, bool records, rtg::BvhReadback& rb) {
     const int64_t F = d->num_faces;
+    const bool anyUV = rtg::any_uv(d), anyMapped = rtg::any_mapped(d);
     const size_t maxNodes = (size_t)2 * F + 1;          // <= 2n - 1 per mesh, + the pad node
     HIP_TRY(sc->nodes.alloc(2 * maxNodes));
     HIP_TRY(sc->node_ext.alloc(maxNodes));
@@ -289,6 +270,8 @@ static int build_bvh_on_device(rtg_scene* sc, const rtg_scene_desc* d, bool anyU
     Free freePerm{dperm};
     hipStream_t st = nullptr;
     int nodeBase = 0;
+    rb.mesh_begin.resize(d->num_meshes);
+    rb.mesh_end.resize(d->num_meshes);
     for (int m = 0; m < d->num_meshes; ++m) {
         const rtg_mesh& M = d->meshes[m];
         if (M.face_count <= 0 || M.face_offset < 0 || M.face_offset + (int64_t)M.face_count > F)
@@ -304,535 +287,68 @@ static int build_bvh_on_device(rtg_scene* sc, const rtg_scene_desc* d, bool anyU
                                     M.face_offset, nodeBase, sc->nodes.p, sc->node_ext.p, sc->tris.p, sc->face_n.p,
                                     anyUV ? sc->face_uv.p : nullptr, anyMapped ? sc->face_v12.p : nullptr,
                                     dperm + M.face_offset, &count, &bl, st));
-        meshBegin[m] = nodeBase;
-        meshEnd[m] = nodeBase + count;
+        rb.mesh_begin[m] = nodeBase;
+        rb.mesh_end[m] = nodeBase + count;
         nodeBase += count;
-        bigleaf |= bl;
+        rb.bigleaf |= bl;
     }
-    sc->node_count = nodeBase + 1;                      // + the zeroed pad node
-    facePerm.resize(F);
-    HIP_TRY(hipMemcpy(facePerm.data(), dperm, F * sizeof(int), hipMemcpyDeviceToHost));
+    rb.node_count = nodeBase + 1;                       // + the zeroed pad node
+    rb.perm.resize(F);
+    HIP_TRY(hipMemcpy(rb.perm.data(), dperm, F * sizeof(int), hipMemcpyDeviceToHost));
     for (int m = 0; m < d->num_meshes; ++m)
-        for (int k = 0; k < d->meshes[m].face_count; ++k) facePerm[d->meshes[m].face_offset + k] += d->meshes[m].face_offset;
+        for (int k = 0; k < d->meshes[m].face_count; ++k) rb.perm[d->meshes[m].face_offset + k] += d->meshes[m].face_offset;
+    if (records) {
+        rb.nodes.resize(2 * (size_t)rb.node_count);
+        HIP_TRY(hipMemcpy(rb.nodes.data(), sc->nodes.p, rb.nodes.size() * sizeof(float4), hipMemcpyDeviceToHost));
+        rb.ext.resize((size_t)rb.node_count);
+        HIP_TRY(hipMemcpy(rb.ext.data(), sc->node_ext.p, rb.ext.size() * sizeof(int2), hipMemcpyDeviceToHost));
+        rb.tris.resize(3 * (size_t)F);
+        HIP_TRY(hipMemcpy(rb.tris.data(), sc->tris.p, rb.tris.size() * sizeof(float4), hipMemcpyDeviceToHost));
+    }
     return RTG_OK;
 }
 
-// The reference's BVH (mesh.cpp:23-156, as the description carries it) re-laid in pre-order
-// with skip links (rtg_device.hpp): a stackless walk "hit -> i+1, miss or leaf done -> skip"
-// visits boxes and faces in the order of BVH::IntersectBVH's recursion (bvh.cpp:5-30).
-static int reference_preorder(const rtg_scene_desc* d, std::vector<float4>& nodes, std::vector<int2>& next,
-                              std::vector<int>& meshBegin, std::vector<int>& meshEnd, bool& bigleaf) {
-    nodes.reserve(2 * d->num_nodes); next.reserve(d->num_nodes);
-    for (int m = 0; m < d->num_meshes; ++m) {
-        const rtg_mesh& M = d->meshes[m];
-        const rtg_bvh_node* N = d->nodes + M.node_offset;
-        const int base = (int)(nodes.size() / 2);
-        meshBegin[m] = base;
-        // pre-order, recording each node's subtree end for the skip link
-        std::vector<int> order;
-        order.reserve(M.node_count);
-        std::vector<int> stack{0};
-        while (!stack.empty()) {
-            int k = stack.back();
-            stack.pop_back();
-            if (k < 0 || k >= M.node_count) return set_err(RTG_ERR_INVALID, "mesh %d: corrupt BVH", m);
-            order.push_back(k);
-            if (N[k].left >= 0) { stack.push_back(N[k].left + 1); stack.push_back(N[k].left); }
-        }
-        std::vector<int> pos(M.node_count, -1);
-        for (size_t i = 0; i < order.size(); ++i) pos[order[i]] = (int)i;
-        std::vector<int> size(M.node_count, 1);
-        for (int i = (int)order.size() - 1; i >= 0; --i) {
-            int k = order[i];
-            if (N[k].left >= 0) size[k] = 1 + size[N[k].left] + size[N[k].left + 1];
-        }
-        for (int k : order) {
-            const rtg_bvh_node& n = N[k];
-            int skip = base + pos[k] + size[k];
-            const int first = M.face_offset + n.first;
-            int leaf = -1;
-            if (n.left < 0) leaf = (first < (1 << 23) && n.count < 255) ? (first << 8) | n.count : rtg::LEAF_EXT;
-            if (n.left < 0 && n.count > rtg::kBigLeaf) bigleaf = true;
-            float4 a, b;
-            a.x = n.bmin[0]; a.y = n.bmin[1]; a.z = n.bmin[2]; a.w = n.bmax[0];
-            b.x = n.bmax[1]; b.y = n.bmax[2];
-            std::memcpy(&b.z, &skip, 4);
-            std::memcpy(&b.w, &leaf, 4);
-            nodes.push_back(a); nodes.push_back(b);
-            next.push_back(make_int2(n.left < 0 ? first : -1, n.left < 0 ? n.count : 0));
-        }
-        meshEnd[m] = (int)(nodes.size() / 2);
-    }
-
-    return RTG_OK;
+// The knobs of the table build: RTG_NO_FAST_SHADOW=1 (shadow rays walk the reference BVH
+// top-down), RTG_AHB=ref|split (rtg_ahb.hpp), RTG_NO_COOP=1 (large leaves tested by their own
+// lane), RTG_AHB_VERBOSE=1.
+static rtg::TableOptions table_options() {
+    rtg::TableOptions opt;
+    opt.fast_shadow = !std::getenv("RTG_NO_FAST_SHADOW");
+    const char* am = std::getenv("RTG_AHB");
+    opt.ahb_mode = !am ? rtg::AHB_EXACT : (std::strcmp(am, "ref") == 0 ? rtg::AHB_REF
+                                           : std::strcmp(am, "split") == 0 ? rtg::AHB_SPLIT : rtg::AHB_EXACT);
+    opt.coop = !std::getenv("RTG_NO_COOP");
+    opt.verbose = std::getenv("RTG_AHB_VERBOSE") != nullptr;
+    return opt;
 }
 
-// Any-hit trees of every mesh (rtg_ahb.cpp).  `reach` bounds |A - o| in the mesh's local space
-// for every shadow ray: origins are surface points and ends light points (a directional
-// light's ray matters only inside the scene), so the world box of every object and light,
-// mapped into each object's local space, bounds both.  False (and no trees) when a leaf
-// entry range does not fit its encoding: shadow rays then take the reference walk.
-static bool anyhit_trees(const rtg_scene_desc* d, const std::vector<float4>& nd, const std::vector<int2>& nx,
-                         const std::vector<int>& meshBegin, const std::vector<int>& meshEnd, const float4* htp, int mode,
-                         std::vector<rtg::WNode>& anodes, std::vector<float4>& ahtris, std::vector<int>& aroot,
-                         rtg::AhbStats& ast) {
-    double wlo[3] = {INFINITY, INFINITY, INFINITY}, whi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    auto addp = [&](double x, double y, double z) {
-        const double p[3] = {x, y, z};
-        for (int k = 0; k < 3; ++k) { wlo[k] = std::min(wlo[k], p[k]); whi[k] = std::max(whi[k], p[k]); }
-    };
-    auto xf = [](const double* m, const double* p, double* o) {
-        for (int r = 0; r < 3; ++r) o[r] = m[4 * r] * p[0] + m[4 * r + 1] * p[1] + m[4 * r + 2] * p[2] + m[4 * r + 3];
-    };
-    for (int i = 0; i < d->num_objects; ++i) {
-        const rtg_object& o = d->objects[i];
-        double lo[3], hi[3];
-        if (o.kind == RTG_OBJ_SPHERE) {
-            for (int k = 0; k < 3; ++k) {
-                lo[k] = (&o.center.x)[k] - std::fabs((double)o.radius);
-                hi[k] = (&o.center.x)[k] + std::fabs((double)o.radius);
-            }
-        } else {
-            for (int k = 0; k < 3; ++k) { lo[k] = o.bbox_min[k]; hi[k] = o.bbox_max[k]; }
-        }
-        for (int c = 0; c < 8; ++c) {
-            const double p[3] = {(c & 1) ? hi[0] : lo[0], (c & 2) ? hi[1] : lo[1], (c & 4) ? hi[2] : lo[2]};
-            if (o.kind == RTG_OBJ_INSTANCE) { addp(p[0], p[1], p[2]); continue; }   // world box already
-            double w[3];
-            xf(o.transform, p, w);
-            addp(w[0], w[1], w[2]);
-        }
+// The tables to the device and the DevScene that points at them (the walk and face tables of
+// a device-built BVH are there already).
+static int upload_tables(rtg_scene* sc, const rtg_scene_desc* d, const rtg::SceneTables& T, bool deviceBvh) {
+    sc->node_count = T.node_count;
+    sc->feat = T.feat;
+    sc->shade_sk = T.shade_sk;
+    sc->num_slots = T.num_slots;
+    sc->wave_ok = T.wave_ok;
+    sc->tree_ok = T.tree_ok;
+    sc->path_ok = T.path_ok;
+    if (!deviceBvh) {
+        HIP_TRY(sc->nodes.upload(T.nodes)); HIP_TRY(sc->node_ext.upload(T.node_ext)); HIP_TRY(sc->tris.upload(T.tris));
+        HIP_TRY(sc->face_n.upload(T.face_n)); HIP_TRY(sc->face_uv.upload(T.face_uv)); HIP_TRY(sc->face_v12.upload(T.face_v12));
     }
-    for (int i = 0; i < d->num_point_lights; ++i)
-        addp(d->point_lights[i].position.x, d->point_lights[i].position.y, d->point_lights[i].position.z);
-    for (int i = 0; i < d->num_spot_lights; ++i)
-        addp(d->spot_lights[i].position.x, d->spot_lights[i].position.y, d->spot_lights[i].position.z);
-    for (int i = 0; i < d->num_area_lights; ++i) {
-        const rtg_area_light& L = d->area_lights[i];
-        for (int c = 0; c < 4; ++c) {
-            const double su = (c & 1) ? 0.5 : -0.5, sv = (c & 2) ? 0.5 : -0.5;
-            addp(L.position.x + (L.u.x * su + L.v.x * sv) * L.extent, L.position.y + (L.u.y * su + L.v.y * sv) * L.extent,
-                 L.position.z + (L.u.z * su + L.v.z * sv) * L.extent);
-        }
-    }
-    // reach = the diagonal of the local-space box holding the mesh and every world point (the
-    // distance |A - o| between a face and a shadow ray's origin is below it)
-    std::vector<double> reach(d->num_meshes, 0.0);
-    for (int i = 0; i < d->num_objects; ++i) {
-        const rtg_object& o = d->objects[i];
-        if (o.kind == RTG_OBJ_SPHERE) continue;
-        double lo[3], hi[3];
-        for (int k = 0; k < 3; ++k) { lo[k] = o.bbox_min[k]; hi[k] = o.bbox_max[k]; }
-        for (int c = 0; c < 8 && std::isfinite(wlo[0]); ++c) {
-            const double p[3] = {(c & 1) ? whi[0] : wlo[0], (c & 2) ? whi[1] : wlo[1], (c & 4) ? whi[2] : wlo[2]};
-            double l[3];
-            xf(o.inv_transform, p, l);
-            for (int k = 0; k < 3; ++k) { lo[k] = std::min(lo[k], l[k]); hi[k] = std::max(hi[k], l[k]); }
-        }
-        const double diag = std::sqrt((hi[0] - lo[0]) * (hi[0] - lo[0]) + (hi[1] - lo[1]) * (hi[1] - lo[1]) +
-                                      (hi[2] - lo[2]) * (hi[2] - lo[2]));
-        reach[o.mesh] = std::max(reach[o.mesh], diag);
-    }
-    aroot.assign(d->num_meshes, -1);
-    bool ahbOk = true;
-    for (int m = 0; m < d->num_meshes && ahbOk; ++m) {
-        if (meshEnd[m] <= meshBegin[m]) continue;
-        aroot[m] = rtg::build_ahb(nd, nx, meshBegin[m], meshEnd[m], htp, reach[m], (rtg::AhbMode)mode, anodes,
-                                  ahtris, &ast);
-        if (aroot[m] == -2) ahbOk = false;      // leaf encoding exceeded: shadow rays take the reference walk
-    }
-    if (!ahbOk) { anodes.clear(); ahtris.clear(); aroot.assign(d->num_meshes, -1); }
-    return ahbOk;
-}
-
-int rtg_scene_create(const rtg_scene_desc* d, int device, rtg_scene** out) {
-    if (!d || !out) return set_err(RTG_ERR_INVALID, "null argument");
-    *out = nullptr;
-    // the packet walks address records by 32-bit byte offsets (rtg_common.hpp rec_at)
-    if (d->num_faces > ((int64_t)1 << 25))
-        return set_err(RTG_ERR_INVALID, "%lld faces: at most 2^25 per scene", (long long)d->num_faces);
-    for (int i = 0; i < d->num_mesh_lights; ++i) {
-        const int o = d->mesh_lights ? d->mesh_lights[i].object : -1;
-        if (o < 0 || o >= d->num_objects || d->objects[o].kind != RTG_OBJ_MESH ||
-            d->meshes[d->objects[o].mesh].face_count <= 0)
-            return set_err(RTG_ERR_INVALID, "mesh light %d: bad object", i);
-    }
-    if (d->max_recursion_depth > rtg::max_supported_depth())
-        return set_err(RTG_ERR_UNSUPPORTED, "MaxRecursionDepth %d > %d", d->max_recursion_depth, rtg::max_supported_depth());
-    for (int i = 0; i < d->num_objects; ++i) {
-        const rtg_object& o = d->objects[i];
-        if (o.kind == RTG_OBJ_SPHERE && o.tex_normal >= 0)
-            return set_err(RTG_ERR_UNSUPPORTED, "sphere %d: normal map (the reference leaves the normal unset, "
-                           "sphere.cpp:95-113)", i);
-        if ((o.tex_normal >= d->num_textures) || (o.tex_bump >= d->num_textures))
-            return set_err(RTG_ERR_INVALID, "object %d: bad normal / bump texture", i);
-        if (o.tex_normal >= 0 && d->textures[o.tex_normal].kind == RTG_TEX_IMAGE &&
-            (d->textures[o.tex_normal].image < 0 || d->textures[o.tex_normal].image >= d->num_images))
-            return set_err(RTG_ERR_INVALID, "object %d: normal map without an image", i);
-        if (o.tex_bump >= 0 && d->textures[o.tex_bump].kind == RTG_TEX_IMAGE &&
-            (d->textures[o.tex_bump].image < 0 || d->textures[o.tex_bump].image >= d->num_images))
-            return set_err(RTG_ERR_INVALID, "object %d: bump map without an image", i);
-        if (o.material < 0 || o.material >= d->num_materials) return set_err(RTG_ERR_INVALID, "object %d: bad material", i);
-        if (o.kind != RTG_OBJ_SPHERE && (o.mesh < 0 || o.mesh >= d->num_meshes))
-            return set_err(RTG_ERR_INVALID, "object %d: bad mesh", i);
-    }
-    for (int i = 0; i < d->num_images; ++i)
-        if (d->images[i].channels < 1 || !d->images[i].texels) return set_err(RTG_ERR_INVALID, "image %d: no texels", i);
-
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return set_err(RTG_ERR_HIP, "no HIP device available");
-    if (device < 0 || device >= ndev) return set_err(RTG_ERR_INVALID, "device %d out of range (%d devices)", device, ndev);
-    HIP_TRY(hipSetDevice(device));
-
-    std::unique_ptr<rtg_scene> sc(new (std::nothrow) rtg_scene);
-    if (!sc) return set_err(RTG_ERR_NOMEM, "out of memory");
-    sc->device = device;
-    sc->max_depth = d->max_recursion_depth;
-    sc->cameras.assign(d->cameras, d->cameras + d->num_cameras);
-
-    // Device ingest (desc without a BVH, RTG_LOAD_DEVICE_BVH): face preparation and the
-    // midpoint BVH are built on the GPU (rtg_bvh.hip); otherwise the host-built reference
-    // topology is re-laid here.
-    const bool gpuBuild = d->num_faces > 0 && d->num_nodes == 0;
-    bool anyMapped = false;
-    for (int i = 0; i < d->num_objects; ++i) {
-        const rtg_object& o = d->objects[i];
-        const bool uvmesh = o.kind != RTG_OBJ_SPHERE && d->meshes[o.mesh].has_uv;
-        if ((uvmesh && o.tex_normal >= 0) || ((uvmesh || o.kind == RTG_OBJ_SPHERE) && o.tex_bump >= 0)) anyMapped = true;
-    }
-
-    // ---- BVH: reference topology -> pre-order with skip links (rtg_device.hpp)
-    std::vector<float4> nodes;
-    std::vector<int2> next;
-    bool bigleaf = false;
-    std::vector<int> meshBegin(d->num_meshes), meshEnd(d->num_meshes);
-    if (!gpuBuild) {
-        const int rc = reference_preorder(d, nodes, next, meshBegin, meshEnd, bigleaf);
-        if (rc) return rc;
-    }
-
-    nodes.push_back(make_float4(0.f, 0.f, 0.f, 0.f));     // pad node: walk_bvh prefetches i+1
-    nodes.push_back(make_float4(0.f, 0.f, 0.f, 0.f));
-
-    // ---- faces (already BVH-permuted)
-    bool anyUV = false;
-    for (int m = 0; m < d->num_meshes; ++m) anyUV |= d->meshes[m].has_uv != 0;
-    const size_t hostFaces = gpuBuild ? 0 : (size_t)d->num_faces;
-    std::vector<float4> tris(3 * hostFaces), fn(hostFaces);
-    std::vector<float2> fuv(anyUV ? 3 * hostFaces : 0);
-    std::vector<int> facePerm;      // device build: final position -> desc face (per mesh offset)
-    if (gpuBuild) {
-        int rc = build_bvh_on_device(sc.get(), d, anyUV, anyMapped, meshBegin, meshEnd, bigleaf, facePerm);
-        if (rc) return rc;
-    }
-    for (int64_t f = 0; f < (int64_t)hostFaces; ++f) {
-        const rtg_face& F = d->faces[f];
-        tris[3 * f] = make_float4(F.v0.x, F.v0.y, F.v0.z, 0.f);
-        tris[3 * f + 1] = make_float4(F.v0.x - F.v1.x, F.v0.y - F.v1.y, F.v0.z - F.v1.z, 0.f);
-        tris[3 * f + 2] = make_float4(F.v0.x - F.v2.x, F.v0.y - F.v2.y, F.v0.z - F.v2.z, 0.f);
-        fn[f] = make_float4(F.n.x, F.n.y, F.n.z, 0.f);
-        if (anyUV) {
-            fuv[3 * f] = make_float2(F.uv0[0], F.uv0[1]);
-            fuv[3 * f + 1] = make_float2(F.uv1[0], F.uv1[1]);
-            fuv[3 * f + 2] = make_float2(F.uv2[0], F.uv2[1]);
-        }
-    }
-
-    // ---- objects
-    std::vector<rtg::DevObject> objs(d->num_objects);
-    int feat = 0;
-    for (int i = 0; i < d->num_objects; ++i) {
-        const rtg_object& o = d->objects[i];
-        rtg::DevObject& D = objs[i];
-        std::memset(&D, 0, sizeof(D));
-        D.kind = o.kind;
-        D.material = o.material;
-        D.flags = o.flags;
-        if (o.kind != RTG_OBJ_SPHERE) {
-            D.node_begin = meshBegin[o.mesh];
-            D.node_end = meshEnd[o.mesh];
-            if (d->meshes[o.mesh].has_uv) D.flags |= rtg::OBJF_HAS_UV;
-        }
-        D.tex_diffuse = o.tex_diffuse;
-        D.tex_specular = o.tex_specular;
-        D.tex_replace_all = o.tex_replace_all;
-        // maps only act where the reference reads them: mesh faces with UVs (mesh.cpp:245-358)
-        // and sphere bump maps (sphere.cpp:116-170)
-        const bool uvmesh = o.kind != RTG_OBJ_SPHERE && d->meshes[o.mesh].has_uv;
-        D.tex_normal = uvmesh ? o.tex_normal : -1;
-        D.tex_bump = (uvmesh && o.tex_normal < 0) || o.kind == RTG_OBJ_SPHERE ? o.tex_bump : -1;
-        if (D.tex_normal >= 0 || D.tex_bump >= 0) D.flags |= rtg::OBJF_MAPPED;
-        for (int k = 0; k < 3; ++k) { D.bmin[k] = o.bbox_min[k]; D.bmax[k] = o.bbox_max[k]; }
-        f4(D.mbv, o.motion_blur);
-        f4(D.center, o.center, o.radius);
-        bool ident = true;
-        for (int k = 0; k < 12; ++k) {
-            D.inv[k] = o.inv_transform[k];
-            D.invT[k] = o.inv_transpose[k];
-            D.baseInvT[k] = o.base_inv_transpose[k];
-            ident &= o.inv_transform[k] == ((k % 5 == 0) ? 1.0 : 0.0);
-        }
-        if (ident) D.flags |= rtg::OBJF_IDENTITY;
-        D.id = o.kind == RTG_OBJ_SPHERE ? INT32_MIN : o.id;   // spheres never carry a light's id
-        if (o.kind == RTG_OBJ_SPHERE) feat |= rtg::FEAT_SPHERE;
-        else if (o.kind == RTG_OBJ_INSTANCE) feat |= rtg::FEAT_INSTANCE;
-        else if (!ident || (o.flags & RTG_OBJF_MOTION_BLUR)) feat |= rtg::FEAT_XFORM;
-    }
-    // shadow-ray acceleration (rtg_common.hpp): the any-hit wide BVH (trace_any_wide) and
-    // face -> reference leaf (its exact leaf-box decisions, the deferred leaves' checks).
-    // RTG_NO_FAST_SHADOW=1: shadow rays walk the reference BVH top-down.
-    std::vector<rtg::WNode> anodes;
-    std::vector<float4> ahtris;
-    int ahbMode = rtg::AHB_EXACT;
-    std::vector<int> faceLeaf;
-    for (int i = 0; i < d->num_objects; ++i) objs[i].aroot = -1;
-    if (!std::getenv("RTG_NO_FAST_SHADOW") && d->num_meshes > 0) {
-        std::vector<float4> dn;
-        std::vector<int2> dx;
-        if (gpuBuild) {
-            dn.resize(2 * (size_t)sc->node_count);
-            HIP_TRY(hipMemcpy(dn.data(), sc->nodes.p, dn.size() * sizeof(float4), hipMemcpyDeviceToHost));
-            dx.resize((size_t)sc->node_count);
-            HIP_TRY(hipMemcpy(dx.data(), sc->node_ext.p, dx.size() * sizeof(int2), hipMemcpyDeviceToHost));
-        }
-        const std::vector<float4>& nd = gpuBuild ? dn : nodes;
-        const std::vector<int2>& nx = gpuBuild ? dx : next;
-        auto leafv = [&](int i) { int l; std::memcpy(&l, &nd[2 * i + 1].w, 4); return l; };
-        faceLeaf.assign((size_t)d->num_faces, -1);
-        for (int m = 0; m < d->num_meshes; ++m)
-            for (int p = meshBegin[m]; p < meshEnd[m]; ++p) {
-                const int l = leafv(p);
-                if (l < 0) continue;
-                int first = l >> 8, cnt = l & 255;
-                if (l == rtg::LEAF_EXT) { first = nx[p].x; cnt = nx[p].y; }
-                for (int f = first; f < first + cnt; ++f) faceLeaf[f] = p;
-            }
-
-        // any-hit tree per mesh (anyhit_trees, rtg_ahb.cpp)
-        std::vector<float4> ht;
-        const float4* htp = tris.data();
-        if (gpuBuild) {
-            ht.resize(3 * (size_t)d->num_faces);
-            HIP_TRY(hipMemcpy(ht.data(), sc->tris.p, ht.size() * sizeof(float4), hipMemcpyDeviceToHost));
-            htp = ht.data();
-        }
-        const char* am = std::getenv("RTG_AHB");
-        ahbMode = !am ? rtg::AHB_EXACT : (std::strcmp(am, "ref") == 0 ? rtg::AHB_REF
-                                          : std::strcmp(am, "split") == 0 ? rtg::AHB_SPLIT : rtg::AHB_EXACT);
-        rtg::AhbStats ast;
-        std::vector<int> aroot;
-        anyhit_trees(d, nd, nx, meshBegin, meshEnd, htp, ahbMode, anodes, ahtris, aroot, ast);
-        for (int i = 0; i < d->num_objects; ++i)
-            objs[i].aroot = d->objects[i].kind != RTG_OBJ_SPHERE ? aroot[d->objects[i].mesh] : -1;
-        if (std::getenv("RTG_AHB_VERBOSE"))
-            std::fprintf(stderr, "rtgpu any-hit tree (mode %d): %lld nodes, %lld entries, depth %d, %lld leaf prims, "
-                                 "%lld face prims (%lld on their leaf box)\n",
-                         ahbMode, ast.nodes, ast.entries, ast.max_depth, ast.leaf_prims, ast.face_prims, ast.exact_faces);
-    }
-    // instance groups: runs of consecutive instances without motion blur, chunked by ~sqrt of
-    // the run length, with the exact (min/max) union of the members' world boxes
-    std::vector<float4> gbox(2 * (size_t)d->num_objects, make_float4(0.f, 0.f, 0.f, 0.f));
-    for (int k = 0; k < d->num_objects;) {
-        auto eligible = [&](int i) {
-            return objs[i].kind == rtg::OBJ_INSTANCE && !(objs[i].flags & rtg::OBJF_MOTION_BLUR);
-        };
-        if (!eligible(k)) { ++k; continue; }
-        int e = k;
-        while (e < d->num_objects && eligible(e)) ++e;
-        const int run = e - k;
-        const int gsz = std::max(4, (int)std::lround(std::sqrt((double)run)));
-        for (int g = k; g < e; g += gsz) {
-            const int ge = std::min(e, g + gsz);
-            if (ge - g < 2) continue;
-            float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-            for (int i = g; i < ge; ++i)
-                for (int c = 0; c < 3; ++c) {
-                    mn[c] = std::min(mn[c], objs[i].bmin[c]);
-                    mx[c] = std::max(mx[c], objs[i].bmax[c]);
-                }
-            objs[g].group_end = ge;
-            gbox[2 * g] = make_float4(mn[0], mn[1], mn[2], 0.f);
-            gbox[2 * g + 1] = make_float4(mx[0], mx[1], mx[2], 0.f);
-        }
-        k = e;
-    }
-    // wavefront eligibility: no ray-tree children and no motion blur
-    bool branching = false, blur = false;
-    for (int i = 0; i < d->num_materials; ++i) {
-        int t = d->materials[i].type;
-        branching |= (t == RTG_MAT_MIRROR || t == RTG_MAT_DIELECTRIC || t == RTG_MAT_CONDUCTOR);
-    }
-    for (int i = 0; i < d->num_objects; ++i) blur |= (d->objects[i].flags & RTG_OBJF_MOTION_BLUR) != 0;
-    sc->feat = feat | (bigleaf ? rtg::FEAT_BIGLEAF : 0);
-    // RTG_NO_COOP=1: large leaves tested by their own lane (the sequential walk handles any
-    // leaf size; the cooperative one is only faster)
-    if (std::getenv("RTG_NO_COOP")) sc->feat &= ~rtg::FEAT_BIGLEAF;
-    sc->tree_ok = !blur && d->max_recursion_depth > 0 && branching;
-    sc->wave_ok = !blur && (d->max_recursion_depth <= 0 || !branching);
-    sc->path_ok = !blur;
-    sc->num_slots = d->num_point_lights + d->num_area_lights + d->num_env_lights + d->num_dir_lights +
-                    d->num_spot_lights + d->num_mesh_lights;
-    // shading features: textures / maps (incl. a background texture), BRDFs, env / spot / mesh
-    // lights
-    {
-        int sk = 0;
-        for (int i = 0; i < d->num_objects; ++i)
-            if (objs[i].tex_diffuse >= 0 || objs[i].tex_specular >= 0 || objs[i].tex_replace_all >= 0 ||
-                (objs[i].flags & rtg::OBJF_MAPPED))
-                sk |= rtg::SK_TEX;
-        if (d->bg_texture >= 0) sk |= rtg::SK_TEX;
-        for (int i = 0; i < d->num_materials; ++i)
-            if (d->materials[i].brdf >= 0) sk |= rtg::SK_BRDF;
-        if (d->num_env_lights + d->num_spot_lights + d->num_mesh_lights > 0) sk |= rtg::SK_XLIGHT;
-        sc->shade_sk = sk;
-    }
-    // mesh lights (meshLight.h): their faces in MeshLight::faces order (the BVH-permuted one)
-    std::vector<rtg::DevMeshLight> mls(d->num_mesh_lights);
-    std::vector<rtg::DevLightFace> lfs;
-    for (int i = 0; i < d->num_mesh_lights; ++i) {
-        const rtg_object& o = d->objects[d->mesh_lights[i].object];
-        const rtg_mesh& M = d->meshes[o.mesh];
-        rtg::DevMeshLight& L = mls[i];
-        std::memset(&L, 0, sizeof(L));
-        L.id = o.id;
-        L.face_begin = (int)lfs.size();
-        L.face_count = M.face_count;
-        f4(L.radiance, d->mesh_lights[i].radiance);
-        L.surface_area = M.surface_area;
-        for (int k = 0; k < 12; ++k) L.xf[k] = o.transform[k];
-        for (int f = 0; f < M.face_count; ++f) {
-            const rtg_face& F = d->faces[gpuBuild ? facePerm[M.face_offset + f] : M.face_offset + f];
-            rtg::DevLightFace lf;
-            std::memset(&lf, 0, sizeof(lf));
-            f4(lf.v0, F.v0); f4(lf.v1, F.v1); f4(lf.v2, F.v2);
-            lf.area = F.area;
-            lfs.push_back(lf);
-        }
-    }
-    std::vector<rtg::DevMaterial> mats(d->num_materials);
-    for (int i = 0; i < d->num_materials; ++i) {
-        const rtg_material& m = d->materials[i];
-        rtg::DevMaterial& D = mats[i];
-        std::memset(&D, 0, sizeof(D));
-        D.type = m.type;
-        D.brdf = m.brdf;
-        f4(D.ambient, m.ambient); f4(D.diffuse, m.diffuse); f4(D.specular, m.specular); f4(D.mirror, m.mirror);
-        f4(D.absorption, m.absorption); f4(D.radiance, m.radiance);
-        D.phong_exponent = m.phong_exponent;
-        D.refractive_index = m.refractive_index;
-        D.absorption_index = m.absorption_index;
-        D.roughness = m.roughness;
-    }
-    std::vector<rtg::DevBrdf> brdfs(d->num_brdfs);
-    for (int i = 0; i < d->num_brdfs; ++i) {
-        std::memset(&brdfs[i], 0, sizeof(brdfs[i]));
-        brdfs[i].type = d->brdfs[i].type;
-        brdfs[i].energy_conserving = d->brdfs[i].energy_conserving;
-        brdfs[i].kd_fresnel = d->brdfs[i].kd_fresnel;
-        brdfs[i].exponent = d->brdfs[i].exponent;
-    }
-    std::vector<rtg::DevTexture> texs(d->num_textures);
-    for (int i = 0; i < d->num_textures; ++i) {
-        const rtg_texture& t = d->textures[i];
-        std::memset(&texs[i], 0, sizeof(texs[i]));
-        texs[i].kind = t.kind;
-        texs[i].blend = t.blend;
-        texs[i].image = t.image;
-        texs[i].nearest = t.nearest;
-        texs[i].noise_scale = t.noise_scale;
-        texs[i].bump_factor = t.bump_factor;
-        texs[i].normalizer = t.normalizer;
-        texs[i].noise_abs = t.noise_abs;
-    }
-    // texel pool; each image padded with one extra row + 4 floats so the reference's
-    // edge reads (bilinear p+1, 1-channel RGB reads) stay inside the allocation
-    std::vector<rtg::DevImage> imgs(d->num_images);
-    std::vector<float> pool;
-    for (int i = 0; i < d->num_images; ++i) {
-        const rtg_image& im = d->images[i];
-        imgs[i].width = im.width; imgs[i].height = im.height; imgs[i].channels = im.channels;
-        imgs[i].offset = (long long)pool.size();
-        size_t n = (size_t)im.width * im.height * im.channels;
-        pool.insert(pool.end(), im.texels, im.texels + n);
-        pool.insert(pool.end(), (size_t)im.width * im.channels + 4, 0.f);
-    }
-    std::vector<rtg::DevPointLight> pls(d->num_point_lights);
-    for (int i = 0; i < d->num_point_lights; ++i) {
-        f4(pls[i].pos, d->point_lights[i].position);
-        f4(pls[i].intensity, d->point_lights[i].intensity);
-    }
-    std::vector<rtg::DevAreaLight> als(d->num_area_lights);
-    for (int i = 0; i < d->num_area_lights; ++i) {
-        const rtg_area_light& a = d->area_lights[i];
-        std::memset(&als[i], 0, sizeof(als[i]));
-        f4(als[i].pos, a.position); f4(als[i].normal, a.normal); f4(als[i].radiance, a.radiance);
-        f4(als[i].u, a.u); f4(als[i].v, a.v);
-        als[i].extent = a.extent; als[i].area = a.area;
-    }
-    std::vector<rtg::DevDirLight> dls(d->num_dir_lights);
-    for (int i = 0; i < d->num_dir_lights; ++i) {
-        f4(dls[i].dir, d->dir_lights[i].dir);
-        f4(dls[i].radiance, d->dir_lights[i].radiance);
-    }
-    std::vector<rtg::DevSpotLight> sls(d->num_spot_lights);
-    for (int i = 0; i < d->num_spot_lights; ++i) {
-        const rtg_spot_light& s = d->spot_lights[i];
-        std::memset(&sls[i], 0, sizeof(sls[i]));
-        f4(sls[i].pos, s.position); f4(sls[i].dir, s.dir); f4(sls[i].intensity, s.intensity);
-        sls[i].coverage_deg = s.coverage_deg; sls[i].falloff_deg = s.falloff_deg;
-        sls[i].cos_half_coverage = s.cos_half_coverage; sls[i].cos_half_falloff = s.cos_half_falloff;
-    }
-    std::vector<int> envs(d->num_env_lights);
-    for (int i = 0; i < d->num_env_lights; ++i) {
-        envs[i] = d->env_lights[i].image;
-        if (envs[i] < 0 || envs[i] >= d->num_images) return set_err(RTG_ERR_INVALID, "env light %d: bad image", i);
-    }
-
-    if (!gpuBuild) {
-        sc->node_count = (int)(nodes.size() / 2);
-        HIP_TRY(sc->nodes.upload(nodes)); HIP_TRY(sc->node_ext.upload(next)); HIP_TRY(sc->tris.upload(tris));
-        HIP_TRY(sc->face_n.upload(fn)); HIP_TRY(sc->face_uv.upload(fuv));
-    }
-    if (anyMapped && !gpuBuild) {
-        std::vector<float4> v12(2 * d->num_faces);
-        for (int64_t f = 0; f < d->num_faces; ++f) {
-            const rtg_face& F = d->faces[f];
-            v12[2 * f] = make_float4(F.v1.x, F.v1.y, F.v1.z, 0.f);
-            v12[2 * f + 1] = make_float4(F.v2.x, F.v2.y, F.v2.z, 0.f);
-        }
-        HIP_TRY(sc->face_v12.upload(v12));
-    }
-    HIP_TRY(sc->objects.upload(objs)); HIP_TRY(sc->group_box.upload(gbox)); HIP_TRY(sc->materials.upload(mats)); HIP_TRY(sc->brdfs.upload(brdfs));
-    HIP_TRY(sc->textures.upload(texs)); HIP_TRY(sc->images.upload(imgs)); HIP_TRY(sc->texels.upload(pool));
-    HIP_TRY(sc->point_lights.upload(pls)); HIP_TRY(sc->area_lights.upload(als)); HIP_TRY(sc->dir_lights.upload(dls));
-    HIP_TRY(sc->spot_lights.upload(sls)); HIP_TRY(sc->env_images.upload(envs));
-    {
-        // env_direction's key-independent inner hashes: mix64(RP_ENV << 32 | e * 16384 + j)
-        auto mix = [](uint64_t z) {
-            z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ULL;
-            z = (z ^ (z >> 27)) * 0x94d049bb133111ebULL;
-            return z ^ (z >> 31);
-        };
-        std::vector<unsigned long long> em((size_t)d->num_env_lights * rtg::kEnvDraws);
-        for (int e = 0; e < d->num_env_lights; ++e)
-            for (int j = 0; j < rtg::kEnvDraws; ++j)
-                em[(size_t)e * rtg::kEnvDraws + j] =
-                    mix(((uint64_t)rtg::kRpEnv << 32) | (uint32_t)((uint32_t)e * 16384u + (uint32_t)j));
-        HIP_TRY(sc->env_mix.upload(em));
-    }
-    HIP_TRY(sc->mesh_lights.upload(mls)); HIP_TRY(sc->light_faces.upload(lfs));
-    HIP_TRY(sc->anodes.upload(anodes));
-    HIP_TRY(sc->ahtris.upload(ahtris));
-    HIP_TRY(sc->face_leaf.upload(faceLeaf));
-    std::vector<rtg::DevCounters> zero(1);
-    std::memset(zero.data(), 0, sizeof(rtg::DevCounters));
-    HIP_TRY(sc->counters.upload(zero));
-    {
-        std::vector<int> perm(512);
-        for (int i = 0; i < 512; ++i) perm[i] = kPerm256[i & 255];
-        HIP_TRY(sc->perm.upload(perm));
-        HIP_TRY(sc->grad.upload(std::vector<float>(kGrad, kGrad + 36)));
-    }
+    HIP_TRY(sc->objects.upload(T.objects)); HIP_TRY(sc->group_box.upload(T.group_box));
+    HIP_TRY(sc->materials.upload(T.materials)); HIP_TRY(sc->brdfs.upload(T.brdfs));
+    HIP_TRY(sc->textures.upload(T.textures)); HIP_TRY(sc->images.upload(T.images)); HIP_TRY(sc->texels.upload(T.texels));
+    HIP_TRY(sc->point_lights.upload(T.point_lights)); HIP_TRY(sc->area_lights.upload(T.area_lights));
+    HIP_TRY(sc->dir_lights.upload(T.dir_lights)); HIP_TRY(sc->spot_lights.upload(T.spot_lights));
+    HIP_TRY(sc->env_images.upload(T.env_images)); HIP_TRY(sc->env_mix.upload(T.env_mix));
+    HIP_TRY(sc->mesh_lights.upload(T.mesh_lights)); HIP_TRY(sc->light_faces.upload(T.light_faces));
+    HIP_TRY(sc->anodes.upload(T.anodes)); HIP_TRY(sc->ahtris.upload(T.ahtris)); HIP_TRY(sc->face_leaf.upload(T.face_leaf));
+    HIP_TRY(sc->perm.upload(T.perm)); HIP_TRY(sc->grad.upload(T.grad));
+    HIP_TRY(sc->counters.alloc(1));
+    HIP_TRY(hipMemset(sc->counters.p, 0, sizeof(rtg::DevCounters)));
+    HIP_TRY(sc->guard.alloc(1));
+    HIP_TRY(hipMemset(sc->guard.p, 0, sizeof(int)));
 
     rtg::DevScene& S = sc->ds;
     std::memset(&S, 0, sizeof(S));
@@ -855,20 +371,51 @@ int rtg_scene_create(const rtg_scene_desc* d, int device, rtg_scene** out) {
     S.ambient[0] = d->ambient_light.x; S.ambient[1] = d->ambient_light.y; S.ambient[2] = d->ambient_light.z;
     for (int k = 0; k < 3; ++k) S.background[k] = d->background[k];
     S.coop = (sc->feat & rtg::FEAT_BIGLEAF) ? 1 : 0;
-    S.anodes = anodes.empty() ? nullptr : sc->anodes.p;
-    S.ahtris = ahtris.empty() ? nullptr : sc->ahtris.p;
-    S.ahb_split = ahbMode == rtg::AHB_SPLIT && !anodes.empty();
+    S.anodes = sc->anodes.p;            // null without trees: DevBuf::upload of an empty table
+    S.ahtris = sc->ahtris.p;
+    S.ahb_split = T.ahb_split;
+    S.face_leaf = sc->face_leaf.p;
+    S.guard = sc->guard.p;
     S.num_faces = (int)d->num_faces;
     S.num_textures = d->num_textures;
     S.num_images = d->num_images;
     S.num_materials = d->num_materials;
-    HIP_TRY(sc->guard.alloc(1));
-    HIP_TRY(hipMemset(sc->guard.p, 0, sizeof(int)));
-    S.guard = sc->guard.p;
-    S.face_leaf = faceLeaf.empty() ? nullptr : sc->face_leaf.p;
     HIP_TRY(hipStreamCreateWithFlags(&sc->stream, hipStreamNonBlocking));
     HIP_TRY(hipEventCreateWithFlags(&sc->done, hipEventDisableTiming));
     HIP_TRY(hipDeviceSynchronize());
+    return RTG_OK;
+}
+
+// Validate, find the device, build the BVH there when the description carries none (device
+// ingest, RTG_LOAD_DEVICE_BVH; otherwise the host-built reference topology is re-laid), build the
+// tables on the host (scene_tables.cpp), upload them.
+int rtg_scene_create(const rtg_scene_desc* d, int device, rtg_scene** out) {
+    if (!d || !out) return set_err(RTG_ERR_INVALID, "null argument");
+    *out = nullptr;
+    std::string err;
+    int rc = rtg::validate_desc(d, err);
+    if (rc) return set_err(rc, "%s", err.c_str());
+
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return set_err(RTG_ERR_HIP, "no HIP device available");
+    if (device < 0 || device >= ndev) return set_err(RTG_ERR_INVALID, "device %d out of range (%d devices)", device, ndev);
+    HIP_TRY(hipSetDevice(device));
+    std::unique_ptr<rtg_scene> sc(new (std::nothrow) rtg_scene);
+    if (!sc) return set_err(RTG_ERR_NOMEM, "out of memory");
+    sc->device = device;
+    sc->max_depth = d->max_recursion_depth;
+    sc->cameras.assign(d->cameras, d->cameras + d->num_cameras);
+
+    const rtg::TableOptions opt = table_options();
+    const bool deviceBvh = d->num_faces > 0 && d->num_nodes == 0;
+    rtg::BvhReadback rb;
+    if (deviceBvh && (rc = build_bvh_on_device(sc.get(), d, opt.fast_shadow, rb))) return rc;
+
+    rtg::SceneTables T;
+    rc = rtg::build_scene_tables(d, opt, deviceBvh ? &rb : nullptr, T, err);
+    if (rc) return set_err(rc, "%s", err.c_str());
+
+    if ((rc = upload_tables(sc.get(), d, T, deviceBvh))) return rc;
     *out = sc.release();
     return RTG_OK;
 }
@@ -982,15 +529,35 @@ static void dev_camera(const rtg_camera& c, rtg::DevCamera& C) {
     C.importance_sampling = c.importance_sampling; C.russian_roulette = c.russian_roulette;
 }
 
+// Camera i of scene s; with `image`, one that has pixels.
+static int scene_camera(const rtg_scene* s, int i, bool image, const rtg_camera*& c) {
+    if (i < 0 || i >= (int)s->cameras.size()) return set_err(RTG_ERR_INVALID, "bad camera %d", i);
+    c = &s->cameras[i];
+    if (image && (c->width <= 0 || c->height <= 0)) return set_err(RTG_ERR_INVALID, "camera %d has an empty image", i);
+    return RTG_OK;
+}
+
+// The rows [row_begin, row_end) a render's options name in an image of `height` rows.
+static void clamp_rows(const rtg_render_opts* o, int height, int& row_begin, int& row_end) {
+    row_begin = o->row_begin < 0 ? 0 : o->row_begin;
+    row_end = (o->row_end <= 0 || o->row_end > height) ? height : o->row_end;
+}
+
+// A scene and its replicas (rtg_scene_create_multi).
+static std::vector<rtg_scene*> with_replicas(rtg_scene* s) {
+    std::vector<rtg_scene*> reps(1, s);
+    reps.insert(reps.end(), s->replicas.begin(), s->replicas.end());
+    return reps;
+}
+
 static int prepare(rtg_scene* s, const rtg_render_opts* o, rtg::DevCamera& C, rtg::RenderParams& P) {
     if (!s || !o) return set_err(RTG_ERR_INVALID, "null argument");
-    if (o->camera < 0 || o->camera >= (int)s->cameras.size()) return set_err(RTG_ERR_INVALID, "bad camera %d", o->camera);
-    const rtg_camera& c = s->cameras[o->camera];
-    if (c.width <= 0 || c.height <= 0) return set_err(RTG_ERR_INVALID, "camera %d has an empty image", o->camera);
+    const rtg_camera* cam = nullptr;
+    if (int rc = scene_camera(s, o->camera, true, cam)) return rc;
+    const rtg_camera& c = *cam;
     dev_camera(c, C);
     std::memset(&P, 0, sizeof(P));
-    P.row_begin = o->row_begin < 0 ? 0 : o->row_begin;
-    P.row_end = (o->row_end <= 0 || o->row_end > c.height) ? c.height : o->row_end;
+    clamp_rows(o, c.height, P.row_begin, P.row_end);
     if (P.row_begin >= P.row_end) return set_err(RTG_ERR_INVALID, "empty row range");
     P.sample_begin = o->sample_begin < 0 ? 0 : o->sample_begin;
     P.sample_count = o->sample_count < 0 ? C.spp : o->sample_count;
@@ -1274,8 +841,8 @@ int rtg_render_device(rtg_scene* s, const rtg_render_opts* o, float* d_hdr, uint
 // the same offsets of the host frame (layout 3*(x + y*width), main.cpp:109).
 static int copy_part(const rtg_render_opts* o, int width, int height, const float* d_hdr, const uint8_t* d_ldr,
                      float* hdr, uint8_t* ldr, hipStream_t st) {
-    const int rb = o->row_begin < 0 ? 0 : o->row_begin;
-    const int re = (o->row_end <= 0 || o->row_end > height) ? height : o->row_end;
+    int rb, re;
+    clamp_rows(o, height, rb, re);
     int32_t n = 0;
     int rc = rtg_part_runs(rb, re, o->part_index, o->part_count, nullptr, 0, &n);
     if (rc) return rc;
@@ -1293,10 +860,10 @@ static int copy_part(const rtg_render_opts* o, int width, int height, const floa
 int rtg_copy_part_to_host(rtg_scene* s, const rtg_render_opts* o, const float* d_hdr, const uint8_t* d_ldr,
                           float* hdr_rgb, uint8_t* ldr_rgb, void* stream) {
     if (!s || !o) return set_err(RTG_ERR_INVALID, "null argument");
-    if (o->camera < 0 || o->camera >= (int)s->cameras.size()) return set_err(RTG_ERR_INVALID, "bad camera %d", o->camera);
-    const rtg_camera& c = s->cameras[o->camera];
+    const rtg_camera* c = nullptr;
+    if (int rc = scene_camera(s, o->camera, false, c)) return rc;
     HIP_TRY(hipSetDevice(s->device));
-    return copy_part(o, c.width, c.height, d_hdr, d_ldr, hdr_rgb, ldr_rgb, (hipStream_t)stream);
+    return copy_part(o, c->width, c->height, d_hdr, d_ldr, hdr_rgb, ldr_rgb, (hipStream_t)stream);
 }
 
 // (Round 4's overlapped host path -- the frame rendered in row chunks on two streams, each
@@ -1331,13 +898,13 @@ static bool host_direct() {
 int rtg_render(rtg_scene* s, const rtg_render_opts* o, float* hdr_rgb, uint8_t* ldr_rgb) {
     if (!s || !o) return set_err(RTG_ERR_INVALID, "null argument");
     if (o->flags & RTG_RENDER_ACCUM_ONLY) return set_err(RTG_ERR_INVALID, "use rtg_render_device for RTG_RENDER_ACCUM_ONLY");
-    std::vector<rtg_scene*> reps(1, s);
-    reps.insert(reps.end(), s->replicas.begin(), s->replicas.end());
+    const std::vector<rtg_scene*> reps = with_replicas(s);
     const int n = (int)reps.size();
     if (n > 1 && o->part_count > 1)
         return set_err(RTG_ERR_INVALID, "a multi-device scene deals its own partition (part_count must be <= 1)");
-    if (o->camera < 0 || o->camera >= (int)s->cameras.size()) return set_err(RTG_ERR_INVALID, "bad camera %d", o->camera);
-    const rtg_camera& cam = s->cameras[o->camera];
+    const rtg_camera* camp = nullptr;
+    if (int rc = scene_camera(s, o->camera, false, camp)) return rc;
+    const rtg_camera& cam = *camp;
     std::vector<rtg_render_opts> ro(n, *o);
     bool whole = false;
     if (n == 1 && host_direct() && !cam.has_tonemapper && (hdr_rgb || ldr_rgb)) {
@@ -1468,14 +1035,12 @@ int rtg_trace_rays(rtg_scene* s, const rtg_ray* rays, int64_t n, uint32_t flags,
 static int camera_rays_args(const rtg_scene* s, const rtg_render_opts* o, const void* rays, rtg::DevCamera& C,
                             int& row_begin, int& row_end) {
     if (!s || !o || !rays) return set_err(RTG_ERR_INVALID, "null argument");
-    if (o->camera < 0 || o->camera >= (int)s->cameras.size()) return set_err(RTG_ERR_INVALID, "bad camera %d", o->camera);
-    const rtg_camera& c = s->cameras[o->camera];
-    if (c.width <= 0 || c.height <= 0) return set_err(RTG_ERR_INVALID, "camera %d has an empty image", o->camera);
-    dev_camera(c, C);
-    row_begin = o->row_begin < 0 ? 0 : o->row_begin;
-    row_end = (o->row_end <= 0 || o->row_end > c.height) ? c.height : o->row_end;
+    const rtg_camera* c = nullptr;
+    if (int rc = scene_camera(s, o->camera, true, c)) return rc;
+    dev_camera(*c, C);
+    clamp_rows(o, c->height, row_begin, row_end);
     if (row_begin >= row_end) return set_err(RTG_ERR_INVALID, "empty row range");
-    if ((int64_t)c.width * c.height > INT32_MAX) return set_err(RTG_ERR_INVALID, "image of more than INT32_MAX pixels");
+    if ((int64_t)c->width * c->height > INT32_MAX) return set_err(RTG_ERR_INVALID, "image of more than INT32_MAX pixels");
     return RTG_OK;
 }
 
@@ -1515,16 +1080,15 @@ static int radiance_args(const rtg_scene* s, const rtg_radiance_opts* o, const v
     if (o->first_pixel < 0) return set_err(RTG_ERR_INVALID, "negative first_pixel %d", o->first_pixel);
     if (n > 0 && (!rays || !rgbt)) return set_err(RTG_ERR_INVALID, "null buffer");
     if (!s) return set_err(RTG_ERR_INVALID, "null scene");
-    if (o->camera < 0 || o->camera >= (int)s->cameras.size()) return set_err(RTG_ERR_INVALID, "bad camera %d", o->camera);
-    const rtg_camera& c = s->cameras[o->camera];
-    if (c.width <= 0 || c.height <= 0) return set_err(RTG_ERR_INVALID, "camera %d has an empty image", o->camera);
+    const rtg_camera* c = nullptr;
+    if (int rc = scene_camera(s, o->camera, true, c)) return rc;
     if (host_ids)
         for (int64_t i = 0; i < n; ++i)
             if (host_ids[i] < 0) return set_err(RTG_ERR_INVALID, "negative pixel id %d at ray %lld", host_ids[i], (long long)i);
     // the frame stack's depth: rtg_scene_create's own bound, kept with the kernel that relies on it
     if (s->max_depth > rtg::max_supported_depth())
         return set_err(RTG_ERR_UNSUPPORTED, "MaxRecursionDepth %d > %d", s->max_depth, rtg::max_supported_depth());
-    dev_camera(c, C);
+    dev_camera(*c, C);
     std::memset(&P, 0, sizeof(P));
     P.n = (int)n;
     P.first_pixel = o->first_pixel;
@@ -1677,10 +1241,8 @@ int rtg_resolve_accum(const float* accum, int32_t w, int32_t h, float* hdr, uint
 
 int rtg_scene_stats(rtg_scene* s, rtg_stats* out) {
     if (!s || !out) return set_err(RTG_ERR_INVALID, "null argument");
-    std::vector<rtg_scene*> reps(1, s);
-    reps.insert(reps.end(), s->replicas.begin(), s->replicas.end());
     std::memset(out, 0, sizeof(*out));
-    for (rtg_scene* r : reps) {
+    for (rtg_scene* r : with_replicas(s)) {
         HIP_TRY(hipSetDevice(r->device));
         rtg::DevCounters c;
         HIP_TRY(hipEventSynchronize(r->done));
@@ -1704,9 +1266,7 @@ int rtg_scene_stats(rtg_scene* s, rtg_stats* out) {
 
 int rtg_scene_reset_stats(rtg_scene* s) {
     if (!s) return set_err(RTG_ERR_INVALID, "null argument");
-    std::vector<rtg_scene*> reps(1, s);
-    reps.insert(reps.end(), s->replicas.begin(), s->replicas.end());
-    for (rtg_scene* r : reps) {
+    for (rtg_scene* r : with_replicas(s)) {
         HIP_TRY(hipSetDevice(r->device));
         HIP_TRY(hipEventSynchronize(r->done));
         // on the scene's (non-blocking) stream, complete before return: ordered before the
@@ -1770,31 +1330,20 @@ extern "C" int rtg_desc_anyhit_check(const rtg_scene_desc* d, int32_t mode, int6
     if (!d || !out || n_out < 8 || mode < 0 || mode > 2) return set_err(RTG_ERR_INVALID, "bad argument");
     if (d->num_faces > 0 && d->num_nodes == 0) return set_err(RTG_ERR_INVALID, "description without a BVH");
     try {
-        std::vector<float4> nodes;
-        std::vector<int2> next;
-        std::vector<int> meshBegin(d->num_meshes), meshEnd(d->num_meshes);
-        bool bigleaf = false;
-        int rc = reference_preorder(d, nodes, next, meshBegin, meshEnd, bigleaf);
-        if (rc) return rc;
-        nodes.push_back(make_float4(0.f, 0.f, 0.f, 0.f));
-        nodes.push_back(make_float4(0.f, 0.f, 0.f, 0.f));
-        std::vector<float4> tris(3 * (size_t)d->num_faces);
-        for (int64_t f = 0; f < d->num_faces; ++f) {
-            const rtg_face& F = d->faces[f];
-            tris[3 * f] = make_float4(F.v0.x, F.v0.y, F.v0.z, 0.f);
-            tris[3 * f + 1] = make_float4(F.v0.x - F.v1.x, F.v0.y - F.v1.y, F.v0.z - F.v1.z, 0.f);
-            tris[3 * f + 2] = make_float4(F.v0.x - F.v2.x, F.v0.y - F.v2.y, F.v0.z - F.v2.z, 0.f);
-        }
-        std::vector<rtg::WNode> anodes;
-        std::vector<float4> ahtris;
-        std::vector<int> aroot;
-        rtg::AhbStats ast;
-        const bool ok = anyhit_trees(d, nodes, next, meshBegin, meshEnd, tris.data(), mode, anodes, ahtris, aroot, ast);
+        std::string err;
+        int rc = rtg::validate_desc(d, err);
+        rtg::TableOptions opt;
+        opt.ahb_mode = (rtg::AhbMode)mode;
+        rtg::SceneTables T;
+        if (!rc) rc = rtg::build_scene_tables(d, opt, nullptr, T, err);
+        if (rc) return set_err(rc, "%s", err.c_str());
+        const bool ok = T.ahb_ok;
         long long bad = 0;
         for (int m = 0; m < d->num_meshes && ok; ++m)
-            bad += rtg::ahb_validate(anodes, ahtris, aroot[m], nodes, next, meshBegin[m], meshEnd[m], tris.data());
-        const int64_t v[8] = {ast.nodes, ast.entries, ast.max_depth, ast.leaf_prims, ast.face_prims, ast.exact_faces,
-                              bad, ok ? 1 : 0};
+            bad += rtg::ahb_validate(T.anodes, T.ahtris, T.aroot[m], T.nodes, T.node_ext, T.mesh_begin[m], T.mesh_end[m],
+                                     T.tris.data());
+        const int64_t v[8] = {T.ahb.nodes, T.ahb.entries, T.ahb.max_depth, T.ahb.leaf_prims, T.ahb.face_prims,
+                              T.ahb.exact_faces, bad, ok ? 1 : 0};
         for (int k = 0; k < 8; ++k) out[k] = v[k];
     } catch (const std::bad_alloc&) {
         return set_err(RTG_ERR_NOMEM, "out of memory");

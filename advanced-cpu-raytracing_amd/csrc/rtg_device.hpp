@@ -1,6 +1,6 @@
 // Device-side data layout for the gfx950 render path.
 //
-// HBM layout (one replica per GPU, built by rtg_scene_create):
+// HBM layout (one replica per GPU; built by build_scene_tables, scene_tables.cpp):
 //   nodes[2i]   float4 {min.x, min.y, min.z, max.x}                     32 B record,
 //   nodes[2i+1] float4 {max.y, max.z, skip (int), leaf (int)}            one cache line
 //     Nodes are the reference's BVH (mesh.cpp:23-156) re-laid in pre-order
