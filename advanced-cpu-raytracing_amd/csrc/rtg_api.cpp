@@ -126,11 +126,11 @@ struct rtg_scene {
     float* d_hdr = nullptr;
     unsigned char* d_ldr = nullptr;
     size_t d_pixels = 0;
-    // scratch of the host-buffer ray queries (rtg_trace_rays, rtg_camera_rays, rtg_radiance_rays):
-    // rays, hits, normals, radiance output, pixel ids; grown on demand, never touched by the
-    // device-buffer entry points
-    void* q_mem[5] = {};
-    size_t q_cap[5] = {};
+    // scratch of the host-buffer ray queries (rtg_trace_rays, rtg_camera_rays, rtg_radiance_rays,
+    // rtg_surface_rays): rays, hits, normals, radiance output, pixel ids, surface output; grown on
+    // demand, never touched by the device-buffer entry points
+    void* q_mem[6] = {};
+    size_t q_cap[6] = {};
     // block -> tile tables, one per (tiles_x, tiles_y) met (never re-uploaded: kernels of
     // several streams may be reading them)
     std::vector<std::unique_ptr<TileMap>> tile_maps;
@@ -1066,6 +1066,43 @@ int rtg_camera_rays(rtg_scene* s, const rtg_render_opts* o, rtg_ray* rays) {
     HIP_TRY(rtg::launch_camera_rays(C, rb, re, o->sample_begin < 0 ? 0 : o->sample_begin, o->seed,
                                     (rtg_ray*)s->q_mem[0], s->stream));
     HIP_TRY(hipMemcpyAsync(rays, s->q_mem[0], bytes, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return RTG_OK;
+}
+
+// ---- surface queries (rtg_surface.hip)
+// checked in an order that names the argument at fault where the scene is not needed to see it
+static int surface_args(const rtg_scene* s, const void* rays, int64_t n, uint32_t flags, const void* out) {
+    if (flags & RTG_QUERY_ANY_HIT)
+        return set_err(RTG_ERR_INVALID, "surface queries are closest-hit: RTG_QUERY_ANY_HIT in flags 0x%x", flags);
+    if (flags & ~(uint32_t)RTG_QUERY_COHERENT) return set_err(RTG_ERR_INVALID, "unknown query flags 0x%x", flags);
+    if (n < 0 || n > INT32_MAX) return set_err(RTG_ERR_INVALID, "%lld rays: at most INT32_MAX per call", (long long)n);
+    if (n > 0 && (!rays || !out)) return set_err(RTG_ERR_INVALID, "null buffer");
+    if (!s) return set_err(RTG_ERR_INVALID, "null scene");
+    return RTG_OK;
+}
+
+int rtg_surface_rays_device(rtg_scene* s, const rtg_ray* d_rays, int64_t n, uint32_t flags, rtg_surface* d_out,
+                            void* stream) {
+    int rc = surface_args(s, d_rays, n, flags, d_out);
+    if (rc || n == 0) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(rtg::launch_surface(s->ds, s->shade_sk, s->feat, d_rays, (int)n, flags, d_out, (hipStream_t)stream));
+    return RTG_OK;
+}
+
+int rtg_surface_rays(rtg_scene* s, const rtg_ray* rays, int64_t n, uint32_t flags, rtg_surface* out) {
+    int rc = surface_args(s, rays, n, flags, out);
+    if (rc || n == 0) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t N = (size_t)n;
+    if ((rc = query_scratch(s, 0, N * sizeof(rtg_ray)))) return rc;
+    if ((rc = query_scratch(s, 5, N * sizeof(rtg_surface)))) return rc;
+    rtg_ray* dr = (rtg_ray*)s->q_mem[0];
+    rtg_surface* ds = (rtg_surface*)s->q_mem[5];
+    HIP_TRY(hipMemcpyAsync(dr, rays, N * sizeof(rtg_ray), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(rtg::launch_surface(s->ds, s->shade_sk, s->feat, dr, (int)n, flags, ds, s->stream));
+    HIP_TRY(hipMemcpyAsync(out, ds, N * sizeof(rtg_surface), hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
     return RTG_OK;
 }

@@ -68,6 +68,12 @@ hipError_t launch_query(const DevScene& S, int feat, const rtg_ray* rays, int n,
                         float4* normals, hipStream_t stream);
 hipError_t launch_camera_rays(const DevCamera& C, int row_begin, int row_end, int sample, unsigned long long seed,
                               rtg_ray* rays, hipStream_t stream);
+// surface queries (rtg_surface.hip): closest hit of n rays, one ray per lane, with the hit's shading
+// normal (normal / bump maps applied), texture coordinates, geometric normal, material and
+// GetDiffuse's coefficient; flags: RTG_QUERY_COHERENT only.  sk / feat as for launch_mega (a scene
+// without SK_TEX runs the variant compiled without maps and texture fetches: the same values).
+hipError_t launch_surface(const DevScene& S, int sk, int feat, const rtg_ray* rays, int n, uint32_t flags, rtg_surface* out,
+                          hipStream_t stream);
 // radiance queries (rtg_radiance.hip): the fused kernel's ray tree below n caller rays, one ray per
 // lane; ray i plays pixel ids ? ids[i] : first_pixel + i (RNG key, background-texture lookup).
 // Of C: the renderer flags, width / height and -- with camera_eye -- the position.  sk / feat as

@@ -40,6 +40,10 @@ RTG_RADIANCE_CAMERA_EYE = 1
 RAY_DTYPE = np.dtype([("ox", "<f4"), ("oy", "<f4"), ("oz", "<f4"), ("tmax", "<f4"),
                       ("dx", "<f4"), ("dy", "<f4"), ("dz", "<f4"), ("time", "<f4")])
 HIT_DTYPE = np.dtype([("t", "<f4"), ("object", "<i4"), ("face", "<i4"), ("pad", "<i4")])
+# rtg_surface (64 B): hit, shading normal + u, geometric normal + v, diffuse coefficient
+SURFACE_DTYPE = np.dtype([("t", "<f4"), ("object", "<i4"), ("face", "<i4"), ("material", "<i4"),
+                          ("n", "<f4", (3,)), ("u", "<f4"), ("ng", "<f4", (3,)), ("v", "<f4"),
+                          ("kd", "<f4", (3,)), ("pad", "<f4")])
 RTG_CAMERA_SIZE = 392   # sizeof(rtg_camera), checked against the C compiler by tests/test_abi.py
 
 
@@ -120,6 +124,7 @@ EXPORTED = [
     "rtg_host_alloc", "rtg_host_free", "rtg_host_register", "rtg_host_unregister",
     "rtg_trace_rays_device", "rtg_trace_rays", "rtg_camera_rays_device", "rtg_camera_rays", "rtg_desc_trace_rays",
     "rtg_radiance_rays_device", "rtg_radiance_rays",
+    "rtg_surface_rays_device", "rtg_surface_rays",
 ]
 
 _lib = None
@@ -185,6 +190,8 @@ def lib() -> ctypes.CDLL:
     L.rtg_desc_trace_rays.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_uint32, vp, vp]
     L.rtg_radiance_rays_device.argtypes = [vp, P(RadianceOpts), vp, vp, ctypes.c_int64, vp, vp]
     L.rtg_radiance_rays.argtypes = [vp, P(RadianceOpts), vp, vp, ctypes.c_int64, vp]
+    L.rtg_surface_rays_device.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_uint32, vp, vp]
+    L.rtg_surface_rays.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_uint32, vp]
     _lib = L
     return L
 
@@ -420,6 +427,27 @@ class DeviceScene:
         o = self.radiance_opts(camera, sample, samples, seed, first_pixel, camera_eye)
         _check(lib().rtg_radiance_rays_device(self._s, ctypes.byref(o), rays_ptr or None, ids_ptr or None, n,
                                               out_ptr or None, stream or None))
+
+    def surface(self, rays, coherent: bool = False) -> np.ndarray:
+        """What render() knows about the point each ray hits (rtg_surface_rays; synchronous):
+        SURFACE_DTYPE array.  ``t / object / face`` are trace()'s closest hit and ``ng`` its
+        geometric normal; ``n`` is the shading normal (normal and bump maps applied, not flipped
+        towards the ray), ``u, v`` the texture coordinates, ``material`` the object's material index
+        and ``kd`` the diffuse coefficient after replace_kd / blend_kd / Perlin textures (reported
+        for every hit, also where the render never reads it: emissive and replace_all objects).  A
+        miss: t = tmax, object = face = material = -1, zeros elsewhere.  ``coherent`` is a
+        performance hint, never a different answer."""
+        rays = np.ascontiguousarray(rays, RAY_DTYPE)
+        out = np.zeros(rays.size, SURFACE_DTYPE)
+        _check(lib().rtg_surface_rays(self._s, rays.ctypes.data, rays.size, _query_flags(False, coherent),
+                                      out.ctypes.data))
+        return out
+
+    def surface_device(self, rays_ptr: int, n: int, out_ptr: int, stream: int = 0, coherent: bool = False):
+        """Asynchronous surface() on device buffers (e.g. torch tensor data_ptr()s: n x 32 B rays,
+        n x 64 B out) on ``stream``; allocates nothing."""
+        _check(lib().rtg_surface_rays_device(self._s, rays_ptr or None, n, _query_flags(False, coherent),
+                                             out_ptr or None, stream or None))
 
     def export_bvh(self):
         """(nodes (N, 8) float32, tris (F, 12) float32): the device's walk records."""

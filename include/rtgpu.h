@@ -484,6 +484,56 @@ int rtg_desc_trace_rays(const rtg_scene_desc* desc, const rtg_ray* rays, int64_t
                         rtg_hit* hits, float* normals);
 
 /* ------------------------------------------------------------------------- */
+/* Surface queries: what the renderer knows about the point a ray hits --     */
+/* shading normal, texture coordinates, material and diffuse coefficient.     */
+/* Added symbols and one type only -- RTG_ABI_VERSION stays 6.                */
+/* ------------------------------------------------------------------------- */
+/* 64 B: four 16-byte stores per ray */
+typedef struct {
+    float t; int32_t object, face, material;   /* as rtg_hit; material = objects[object].material, -1 on a miss */
+    float nx, ny, nz, u;                       /* shading normal (world, unit); texture coordinate u */
+    float gx, gy, gz, v;                       /* geometric normal (world, unit); texture coordinate v */
+    float kd_r, kd_g, kd_b, pad;               /* diffuse coefficient; pad = 0 */
+} rtg_surface;
+
+/* Semantics (PerformShading's view of a primary hit, raytracer.cpp:65-134):
+ *  - t, object, face: the closest hit rtg_trace_rays reports for the same ray, bit for bit
+ *    (tmax, ties and the moved-origin rule of motion-blurred instances included).
+ *  - gx, gy, gz: the `normals` output of rtg_trace_rays, bit for bit: the face's or sphere's
+ *    normal through the object's inverse transpose, before any normal or bump map.
+ *  - nx, ny, nz: the normal PerformShading receives for a primary ray: a mesh's replace_normal /
+ *    bump_normal map or a sphere's bump map (image or Perlin) applied in the object's space, then
+ *    the object's inverse transpose.  As in the reference it is not flipped towards the ray.  For
+ *    an object without a normal or bump map it equals g bit for bit.
+ *  - u, v: the texture coordinates the reference's intersection reports.  Mesh with UVs: the
+ *    face's coordinates interpolated with the hit's barycentrics, each through the reference's
+ *    tiling rule (a value above 1.0001 keeps its fractional part; a fractional part below 0.0001
+ *    becomes 1).  Mesh without UVs: 0.  Sphere: u = (pi - atan2(z, x)) / (2 pi), v = acos(y / r) / pi
+ *    of the local hit point relative to the centre.
+ *  - kd_r, kd_g, kd_b: the coefficient GetDiffuse hands to Shade (raytracer.cpp:478-508).  Without
+ *    a diffuse texture it is the material's DiffuseReflectance, bit for bit.  With one it is the
+ *    image sample / 255 (nearest or bilinear) or the Perlin value, replacing the material's value
+ *    (replace_kd) or averaged with it (blend_kd).  It is reported for every hit, also for emissive
+ *    materials and replace_all objects, whose render never reads it.
+ *  - A miss: t = tmax (its bits), object = face = material = -1, every other field +0.0f.
+ *  - flags: RTG_QUERY_COHERENT is a performance hint only: results are bit-identical with and
+ *    without it.  RTG_QUERY_ANY_HIT or an unknown bit is RTG_ERR_INVALID.
+ *  - time is the motion-blur time, as for rtg_trace_rays.
+ *  - The arithmetic is the reference's float32, singular points included: u, v of a ray in or
+ *    near a face's plane carry the barycentrics' error (about 2^-24 / cos(ray, face normal)), and a
+ *    hit on the very pole of a sphere, where rounding puts |y| above r, has acos(y / r) = NaN: v,
+ *    and the normal of a bumped sphere, are NaN there, as in the render.
+ *  - n == 0 is RTG_OK; n above INT32_MAX or a null scene / buffer is RTG_ERR_INVALID.  Without a
+ *    device: RTG_ERR_HIP (no scene can exist). */
+
+/* Device-resident buffers on `stream`: asynchronous, no allocation, and no render state touched.
+ * A multi-device scene answers on its first replica. */
+int rtg_surface_rays_device(rtg_scene* scene, const rtg_ray* d_rays, int64_t n, uint32_t flags,
+                            rtg_surface* d_out, void* stream);
+/* Same on host buffers (synchronous; copies through the scene's query scratch). */
+int rtg_surface_rays(rtg_scene* scene, const rtg_ray* rays, int64_t n, uint32_t flags, rtg_surface* out);
+
+/* ------------------------------------------------------------------------- */
 /* Radiance queries: the colour the renderer computes along caller-supplied   */
 /* rays.  Added symbols and types only -- RTG_ABI_VERSION stays 6.            */
 /* ------------------------------------------------------------------------- */

@@ -13,7 +13,7 @@ renders: RTG_FRAME_KERNEL=0 splits the sample pass into k_primary + k_shade_shad
 RTG_RENDER_EXACT_SHADOW gives k_shadow with the reference walk).  k_primary is the yardstick of
 (a): the same walk on the same rays, with a 32-byte ray read in place of ray generation.
 
-    python tools/query_bench.py [--launches 50] [--reps 3] [--out FILE] [--sections query,radiance]
+    python tools/query_bench.py [--launches 50] [--reps 3] [--out FILE] [--sections query,radiance,surface]
 
 The radiance section (rtg_radiance_rays_device, DeviceScene.radiance_device) runs on the same
 height field and on the path-tracing fixture tests/golden/scenes/pt_cornell.xml at its own size:
@@ -25,6 +25,15 @@ the camera's rays, generated on the device, shaded
 
 against the yardstick of the same session: stage k_render of RTG_RENDER_FUSED | RTG_RENDER_TIMING
 renders -- the same ray trees, with ray generation in place of a 32-byte load.
+
+The surface section (rtg_surface_rays_device, DeviceScene.surface_device) runs on the same height
+field and on the textured fixture tests/golden/scenes/transforms_textures.xml (its camera's rays
+repeated to about a million, so that a launch is not all launch overhead): the camera's rays in
+k_primary's 8x8-tile order and in pixel order, with and without the hint,
+
+  (s)  surface_device: 64 B per ray out        (t)  trace_device with normals: 32 B per ray out
+
+on the same rays in the same session; the ratio (s) / (t) is the figure to read.
 """
 import argparse
 import os
@@ -137,6 +146,101 @@ def radiance_main(args):
     return lines
 
 
+def surface_section(args, name, xml, min_rays):
+    """Timings of one scene: lines of text."""
+    import torch
+
+    import rtgpu
+
+    hs = rtgpu.HostScene(xml)
+    ds = rtgpu.DeviceScene(hs, 0)
+    cam = hs.camera(0)
+    w, h = cam["width"], cam["height"]
+    n0 = w * h
+    dev = torch.device("cuda:0")
+    st = torch.cuda.current_stream().cuda_stream
+    rays0 = torch.empty((n0, 8), dtype=torch.float32, device=dev)
+    ds.camera_rays_device(rays0.data_ptr(), stream=st)
+    torch.cuda.synchronize()
+    rep = max(1, -(-min_rays // n0))
+    n = n0 * rep
+    pixel = rays0.repeat(rep, 1).contiguous()
+    sets = {"pixel": pixel}
+    if w % 8 == 0 and h % 8 == 0:
+        # k_primary's wave shape (rtg_common.hpp tile_pixel): 64 consecutive rays = one 8x8 pixel tile
+        yy, xx = np.divmod(np.arange(n0), w)
+        key = (yy // 8) * (w // 8) * 64 + (xx // 8) * 64 + (yy % 8) * 8 + (xx % 8)
+        order = np.empty(n0, np.int64)
+        order[key] = np.arange(n0)
+        sets["tiled"] = rays0[torch.from_numpy(order).to(dev)].repeat(rep, 1).contiguous()
+    surf = torch.empty((n, 16), dtype=torch.float32, device=dev)
+    hits = torch.empty((n, 4), dtype=torch.int32, device=dev)
+    nrm = torch.empty((n, 4), dtype=torch.float32, device=dev)
+    C = rtgpu.RTG_QUERY_COHERENT
+    cases = []
+    for which in sets:
+        for hint in (True, False):
+            tag = f"{which}{', hint' if hint else ''}"
+            cases.append((f"s  surface, {tag}", which, hint, True))
+            cases.append((f"t  trace + normals, {tag}", which, hint, False))
+
+    def run(which, hint, is_surface, k):
+        buf = sets[which]
+        for _ in range(k):
+            if is_surface:
+                ds.surface_device(buf.data_ptr(), n, surf.data_ptr(), stream=st, coherent=hint)
+            else:
+                ds.trace_device(buf.data_ptr(), n, hits.data_ptr(), nrm.data_ptr(), stream=st, flags=C if hint else 0)
+
+    # the answers first: the hit and the geometric normal of (s) are those of (t), bit for bit
+    for which in sets:
+        for hint in (True, False):
+            run(which, hint, True, 1)
+            run(which, hint, False, 1)
+            torch.cuda.synchronize()
+            assert torch.equal(surf[:, 0:3].view(torch.int32), hits[:, 0:3]), which
+            assert torch.equal(surf[:, 8:11].view(torch.int32), nrm[:, 0:3].view(torch.int32)), which
+    n_hit = int((hits[:, 1] >= 0).sum())
+    for _, which, hint, is_surface in cases:
+        run(which, hint, is_surface, args.warmup)
+    torch.cuda.synchronize()
+    ms = {c[0]: [] for c in cases}
+    for _ in range(args.reps):
+        for label, which, hint, is_surface in cases:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            run(which, hint, is_surface, args.launches)
+            e1.record()
+            e1.synchronize()
+            ms[label].append(e0.elapsed_time(e1) / args.launches)
+    lines = [f"surface: {name} {w}x{h} x {rep}, {n} rays ({n_hit} hits), {args.launches} launches x {args.reps} interleaved "
+             f"repetitions, device {torch.cuda.get_device_name(0)} (t / object / face / ng of every case checked against trace_device)",
+             f"{'case':40s} {'ms (median)':>12s} {'min':>8s} {'max':>8s} {'Grays/s':>9s} {'s / t':>7s}"]
+    for label, which, hint, is_surface in cases:
+        v = ms[label]
+        ratio = ""
+        if is_surface:
+            other = next(c[0] for c in cases if c[1] == which and c[2] == hint and not c[3])
+            ratio = f"{np.median(v) / np.median(ms[other]):7.3f}"
+        lines.append(f"{label:40s} {np.median(v):12.4f} {min(v):8.4f} {max(v):8.4f} {n / np.median(v) / 1e6:9.3f} {ratio:>7s}")
+    spread = lambda v: (max(v) - min(v)) / np.median(v) * 100
+    lines.append("spread over the repetitions: " + ", ".join(f"{spread(ms[c[0]]):.1f} %" for c in cases))
+    return lines
+
+
+def surface_main(args):
+    import scenes
+
+    tmp = tempfile.mkdtemp(prefix="query_bench_")
+    lines = []
+    xml = scenes.synthetic_heightfield(tmp, K=args.K, width=args.width, height=args.height)
+    os.chdir(tmp)
+    lines += surface_section(args, f"synthetic_heightfield K={args.K}", xml, 0)
+    os.chdir(os.path.join(ROOT, "tests", "golden", "scenes"))
+    lines += surface_section(args, "transforms_textures", "transforms_textures.xml", 1 << 20)
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--launches", type=int, default=50)
@@ -155,6 +259,8 @@ def main():
         text += query_main(args)
     if "radiance" in sections:
         text += radiance_main(args)
+    if "surface" in sections:
+        text += surface_main(args)
     text = "\n".join(text)
     print(text)
     if out:
