@@ -395,51 +395,27 @@ void Loader::parseCameras(XmlNode* root) {            // parser.cpp:1498-1636
         stream.line(child ? child->GetText() : nullptr); stream.get(width).get(height);
         child = element->FirstChildElement("ImageName");
         stream.line(child ? child->GetText() : nullptr); stream.get(imageName);
-        int iw = (int)width, ih = (int)height;
-        V3 gaze, up, right, q;
-        float mleft, mright, mbottom, mtop;
+        rtg_camera_view view;
+        std::memset(&view, 0, sizeof(view));
+        view.position = to_f3(camPos); view.up = to_f3(upDir);
+        view.near_dist = nearDist; view.width = (int)width; view.height = (int)height;
+        view.look_at = isLookAt;
+        V3 gazeIn;                                      // the gaze point (lookAt) or direction
         if (isLookAt) {                                 // camera.cpp:25-48
-            V3 gazePoint;
-            float fovY = 0.f;
             child = element->FirstChildElement("GazePoint");
             if (!child) child = element->FirstChildElement("Gaze");
-            stream.line(child ? child->GetText() : nullptr); stream.get(gazePoint.x).get(gazePoint.y).get(gazePoint.z);
+            stream.line(child ? child->GetText() : nullptr); stream.get(gazeIn.x).get(gazeIn.y).get(gazeIn.z);
             child = element->FirstChildElement("FovY");
-            stream.line(child ? child->GetText() : nullptr); stream.get(fovY);
-            float aspect = (float)iw / ih;
-            mtop = nearDist * std::tan((fovY * (M_PI / 180.0f) / 2.0f));
-            mright = mtop * aspect;
-            mbottom = -mtop;
-            mleft = -mright;
-            gaze = makeUnit(gazePoint - camPos);
-            V3 tempUp = makeUnit(upDir);
-            V3 tempRight = makeUnit(cross(tempUp, gaze));
-            up = makeUnit(cross(gaze, tempRight));
+            stream.line(child ? child->GetText() : nullptr); stream.get(view.fov_y);
         } else {                                        // camera.cpp:5-23
-            V3 gazeDir;
-            float np[4] = {0, 0, 0, 0};
+            float* np = view.near_plane;
             child = element->FirstChildElement("Gaze");
-            stream.line(child ? child->GetText() : nullptr); stream.get(gazeDir.x).get(gazeDir.y).get(gazeDir.z);
+            stream.line(child ? child->GetText() : nullptr); stream.get(gazeIn.x).get(gazeIn.y).get(gazeIn.z);
             child = element->FirstChildElement("NearPlane");
             stream.line(child ? child->GetText() : nullptr); stream.get(np[0]).get(np[1]).get(np[2]).get(np[3]);
-            mleft = np[0]; mright = np[1]; mbottom = np[2]; mtop = np[3];
-            gaze = makeUnit(gazeDir);
-            V3 tempUp = makeUnit(upDir);
-            float dotvu = dot(tempUp, gaze);             // Camera::GetOrthonormal camera.cpp:50-58
-            float relativeSqr = dot(gaze, gaze);
-            V3 proj = gaze * (dotvu / relativeSqr);
-            up = makeUnit(tempUp - proj);
         }
-        // CalculateImagePlaneParams (camera.cpp:60-72)
-        V3 middle = camPos + gaze * nearDist;
-        V3 w = -gaze;
-        right = cross(up, w);
-        q = middle + right * mleft + up * mtop;
-
-        cam.position = to_f3(camPos); cam.gaze = to_f3(gaze); cam.up = to_f3(up);
-        cam.right = to_f3(right); cam.q = to_f3(q);
-        cam.left = mleft; cam.right_ext = mright; cam.bottom = mbottom; cam.top = mtop;
-        cam.near_dist = nearDist; cam.width = iw; cam.height = ih;
+        view.gaze = to_f3(gazeIn);
+        camera_setup(view, cam);
         std::memset(cam.image_name, 0, sizeof(cam.image_name));
         std::strncpy(cam.image_name, imageName.c_str(), sizeof(cam.image_name) - 1);
 
@@ -1093,6 +1069,46 @@ void Loader::flatten() {
 }  // namespace
 
 // ---------------------------------------------------------------------------
+void camera_setup(const rtg_camera_view& view, rtg_camera& cam) {
+    const V3 camPos(view.position.x, view.position.y, view.position.z);
+    const V3 upDir(view.up.x, view.up.y, view.up.z);
+    const V3 gazeIn(view.gaze.x, view.gaze.y, view.gaze.z);
+    const float nearDist = view.near_dist;
+    const int iw = view.width, ih = view.height;
+    V3 gaze, up, right, q;
+    float mleft, mright, mbottom, mtop;
+    if (view.look_at) {                                 // camera.cpp:25-48
+        const float fovY = view.fov_y;
+        float aspect = (float)iw / ih;
+        mtop = nearDist * std::tan((fovY * (M_PI / 180.0f) / 2.0f));
+        mright = mtop * aspect;
+        mbottom = -mtop;
+        mleft = -mright;
+        gaze = makeUnit(gazeIn - camPos);
+        V3 tempUp = makeUnit(upDir);
+        V3 tempRight = makeUnit(cross(tempUp, gaze));
+        up = makeUnit(cross(gaze, tempRight));
+    } else {                                            // camera.cpp:5-23
+        mleft = view.near_plane[0]; mright = view.near_plane[1]; mbottom = view.near_plane[2]; mtop = view.near_plane[3];
+        gaze = makeUnit(gazeIn);
+        V3 tempUp = makeUnit(upDir);
+        float dotvu = dot(tempUp, gaze);                 // Camera::GetOrthonormal camera.cpp:50-58
+        float relativeSqr = dot(gaze, gaze);
+        V3 proj = gaze * (dotvu / relativeSqr);
+        up = makeUnit(tempUp - proj);
+    }
+    // CalculateImagePlaneParams (camera.cpp:60-72)
+    V3 middle = camPos + gaze * nearDist;
+    V3 w = -gaze;
+    right = cross(up, w);
+    q = middle + right * mleft + up * mtop;
+
+    cam.position = to_f3(camPos); cam.gaze = to_f3(gaze); cam.up = to_f3(up);
+    cam.right = to_f3(right); cam.q = to_f3(q);
+    cam.left = mleft; cam.right_ext = mright; cam.bottom = mbottom; cam.top = mtop;
+    cam.near_dist = nearDist; cam.width = iw; cam.height = ih;
+}
+
 int HostScene::load(const std::string& path, std::string& err) {
     try {
         Loader L(*this);

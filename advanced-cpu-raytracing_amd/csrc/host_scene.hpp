@@ -43,6 +43,10 @@ struct HostScene {
     void finalize();
 };
 
+// Camera::SetupDefault / SetupLookAt + CalculateImagePlaneParams (camera.cpp:5-72): the view's
+// frame and image plane into `cam` (rtg_camera_setup; the loader's cameras go through it too).
+void camera_setup(const rtg_camera_view& view, rtg_camera& cam);
+
 }  // namespace rtg
 
 struct rtg_host_scene {

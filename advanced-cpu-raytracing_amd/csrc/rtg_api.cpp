@@ -43,20 +43,40 @@ int set_err(int code, const char* fmt, ...) {
 template <typename T>
 struct DevBuf {
     T* p = nullptr;
-    size_t n = 0;
+    size_t n = 0;      // entries in use
+    size_t cap = 0;    // entries allocated (>= n: update() keeps an allocation that is large enough)
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
     ~DevBuf() { if (p) (void)hipFree(p); }
+    // what the kernels are handed: null for an empty table, as after upload()
+    T* ptr() const { return n ? p : nullptr; }
     hipError_t alloc(size_t count) {
         if (p) { (void)hipFree(p); p = nullptr; }
-        n = count;
+        n = cap = count;
         return count ? hipMalloc(&p, count * sizeof(T)) : hipSuccess;
     }
     hipError_t upload(const std::vector<T>& v) {
         if (p) { (void)hipFree(p); p = nullptr; }   // hipFree waits for the device
-        n = v.size();
+        n = cap = v.size();
         if (n == 0) return hipSuccess;
         hipError_t e = hipMalloc(&p, n * sizeof(T));
-        if (e != hipSuccess) return e;
+        if (e != hipSuccess) { n = cap = 0; return e; }
         return hipMemcpy(p, v.data(), n * sizeof(T), hipMemcpyHostToDevice);
+    }
+    // In place on `st` where `v` fits the allocation: work enqueued on `st` before sees the old
+    // entries, work after it the new ones; `v` must outlive the copy.  A table that outgrows its
+    // capacity is reallocated: hipFree waits for the device (every stream's work), and p changes.
+    hipError_t update(const std::vector<T>& v, hipStream_t st) {
+        if (v.size() > cap) {
+            if (p) { (void)hipFree(p); p = nullptr; }
+            n = cap = 0;
+            hipError_t e = hipMalloc(&p, v.size() * sizeof(T));
+            if (e != hipSuccess) return e;
+            cap = v.size();
+        }
+        n = v.size();
+        return n ? hipMemcpyAsync(p, v.data(), n * sizeof(T), hipMemcpyHostToDevice, st) : hipSuccess;
     }
 };
 
@@ -80,38 +100,55 @@ struct TileMap {
     DevBuf<int> map;
 };
 
+// What rtg_scene_update never writes: the geometry and everything derived from it alone.  One
+// copy per created scene, shared with its clones (rtg_scene_clone) by reference count; freed on
+// the device of the scene that drops the last reference (all of them are on the same one).
+struct SceneGeom {
+    DevBuf<float4> nodes, tris, face_n;
+    int node_count = 0;               // nodes in use (device-built BVH: <= nodes.n / 2)
+    DevBuf<int2> node_ext;
+    DevBuf<float2> face_uv;
+    DevBuf<float4> face_v12;
+    DevBuf<rtg::DevLightFace> light_faces;
+    DevBuf<rtg::DevImage> images;
+    DevBuf<float> texels;
+    DevBuf<rtg::WNode> anodes;
+    DevBuf<float4> ahtris;
+    DevBuf<int> face_leaf;
+    DevBuf<int> perm;
+    DevBuf<float> grad;
+};
+
 struct rtg_scene {
     int device = 0;
     rtg::DevScene ds;
     std::vector<rtg_camera> cameras;
     int max_depth = 0;
-    DevBuf<float4> nodes, tris, face_n;
-    int node_count = 0;               // nodes in use (device-built BVH: <= nodes.n / 2)
-    DevBuf<int2> node_ext;
+    std::shared_ptr<SceneGeom> geom;
+    // env_direction's hashes depend on the light's index alone: shared until an update needs more
+    std::shared_ptr<DevBuf<unsigned long long>> env_mix;
+    // the mutable tables (rtg_scene_update copies into them in place)
     DevBuf<int> env_images;
-    DevBuf<unsigned long long> env_mix;
-    DevBuf<float2> face_uv;
-    DevBuf<float4> face_v12;
     DevBuf<rtg::DevMeshLight> mesh_lights;
-    DevBuf<rtg::DevLightFace> light_faces;
     DevBuf<rtg::DevObject> objects;
     DevBuf<float4> group_box;
     DevBuf<rtg::DevMaterial> materials;
     DevBuf<rtg::DevBrdf> brdfs;
     DevBuf<rtg::DevTexture> textures;
-    DevBuf<rtg::DevImage> images;
-    DevBuf<float> texels;
     DevBuf<rtg::DevPointLight> point_lights;
     DevBuf<rtg::DevAreaLight> area_lights;
     DevBuf<rtg::DevDirLight> dir_lights;
     DevBuf<rtg::DevSpotLight> spot_lights;
     DevBuf<rtg::DevCounters> counters;
-    DevBuf<rtg::WNode> anodes;
-    DevBuf<float4> ahtris;
-    DevBuf<int> face_leaf;
     DevBuf<int> guard;                // RTG_GUARD builds: index-violation bits
-    DevBuf<int> perm;
-    DevBuf<float> grad;
+    // rtg_scene_update: the options and kept state of the creation; the host copies of the
+    // mutable tables in effect (the sources of the update's asynchronous copies, and of a
+    // clone's uploads), and the event after those copies -- waited for before `staged` is
+    // overwritten or freed
+    rtg::TableOptions opt;
+    rtg::KeptTables kept;
+    rtg::SceneTables staged;
+    hipEvent_t updated = nullptr;
     bool wave_ok = false;             // scene renders on the wavefront pipeline
     bool tree_ok = false;             // scene may render on the wavefront ray-tree pipeline
     rtg::TreeState* tree = nullptr;   // its buffers
@@ -147,6 +184,10 @@ struct rtg_scene {
     ~rtg_scene() {
         for (rtg_scene* r : replicas) delete r;
         (void)hipSetDevice(device);
+        if (updated) {                // an update's copies may still be reading `staged`
+            (void)hipEventSynchronize(updated);
+            (void)hipEventDestroy(updated);
+        }
         if (guard.p) {
             int bits = 0;
             if (hipMemcpy(&bits, guard.p, sizeof(int), hipMemcpyDeviceToHost) == hipSuccess && bits)
@@ -229,12 +270,13 @@ int rtg_desc_counts(const rtg_scene_desc* d, int64_t* num_objects, int64_t* num_
 int rtg_scene_export_bvh(const rtg_scene* s, float* nodes, int64_t max_nodes, float* tris, int64_t max_faces,
                          int64_t* num_nodes, int64_t* num_faces) {
     if (!s) return set_err(RTG_ERR_INVALID, "null scene");
-    const int64_t nn = s->node_count, nf = (int64_t)(s->tris.n / 3);
+    const SceneGeom& g = *s->geom;
+    const int64_t nn = g.node_count, nf = (int64_t)(g.tris.n / 3);
     if (num_nodes) *num_nodes = nn;
     if (num_faces) *num_faces = nf;
     HIP_TRY(hipSetDevice(s->device));
-    if (nodes && max_nodes >= nn) HIP_TRY(hipMemcpy(nodes, s->nodes.p, nn * 2 * sizeof(float4), hipMemcpyDeviceToHost));
-    if (tris && max_faces >= nf) HIP_TRY(hipMemcpy(tris, s->tris.p, nf * 3 * sizeof(float4), hipMemcpyDeviceToHost));
+    if (nodes && max_nodes >= nn) HIP_TRY(hipMemcpy(nodes, g.nodes.p, nn * 2 * sizeof(float4), hipMemcpyDeviceToHost));
+    if (tris && max_faces >= nf) HIP_TRY(hipMemcpy(tris, g.tris.p, nf * 3 * sizeof(float4), hipMemcpyDeviceToHost));
     return RTG_OK;
 }
 
@@ -250,7 +292,7 @@ int rtg_device_count(int32_t* count) {
 // into the scene's walk buffers; rb receives the node ranges and the final face order (mesh
 // lights sample it) and, with `records`, host copies of the walk records (the any-hit trees
 // are built from them).
-static int build_bvh_on_device(rtg_scene* sc, const rtg_scene_desc* d, bool records, rtg::BvhReadback& rb) {
+static int build_bvh_on_device(SceneGeom* sc, const rtg_scene_desc* d, bool records, rtg::BvhReadback& rb) {
     const int64_t F = d->num_faces;
     const bool anyUV = rtg::any_uv(d), anyMapped = rtg::any_mapped(d);
     const size_t maxNodes = (size_t)2 * F + 1;          // <= 2n - 1 per mesh, + the pad node
@@ -322,47 +364,54 @@ static rtg::TableOptions table_options() {
     return opt;
 }
 
-// The tables to the device and the DevScene that points at them (the walk and face tables of
-// a device-built BVH are there already).
-static int upload_tables(rtg_scene* sc, const rtg_scene_desc* d, const rtg::SceneTables& T, bool deviceBvh) {
-    sc->node_count = T.node_count;
+// The tables rtg_scene_update may write, uploaded afresh (creation, clone).
+static int upload_mutable(rtg_scene* sc, const rtg::SceneTables& T) {
+    HIP_TRY(sc->objects.upload(T.objects)); HIP_TRY(sc->group_box.upload(T.group_box));
+    HIP_TRY(sc->materials.upload(T.materials)); HIP_TRY(sc->brdfs.upload(T.brdfs));
+    HIP_TRY(sc->textures.upload(T.textures));
+    HIP_TRY(sc->point_lights.upload(T.point_lights)); HIP_TRY(sc->area_lights.upload(T.area_lights));
+    HIP_TRY(sc->dir_lights.upload(T.dir_lights)); HIP_TRY(sc->spot_lights.upload(T.spot_lights));
+    HIP_TRY(sc->env_images.upload(T.env_images));
+    HIP_TRY(sc->mesh_lights.upload(T.mesh_lights));
+    // what every scene owns besides: counters, guard, its stream and its events
+    HIP_TRY(sc->counters.alloc(1));
+    HIP_TRY(hipMemset(sc->counters.p, 0, sizeof(rtg::DevCounters)));
+    HIP_TRY(sc->guard.alloc(1));
+    HIP_TRY(hipMemset(sc->guard.p, 0, sizeof(int)));
+    HIP_TRY(hipStreamCreateWithFlags(&sc->stream, hipStreamNonBlocking));
+    HIP_TRY(hipEventCreateWithFlags(&sc->done, hipEventDisableTiming));
+    HIP_TRY(hipEventCreateWithFlags(&sc->updated, hipEventDisableTiming));
+    return RTG_OK;
+}
+
+// The scene's host-side state for description `d` with tables T (built or updated): the pipeline
+// scalars, the cameras and the DevScene pointing at the scene's device tables as they are now.
+static void scene_state(rtg_scene* sc, const rtg_scene_desc* d, const rtg::SceneTables& T) {
     sc->feat = T.feat;
     sc->shade_sk = T.shade_sk;
     sc->num_slots = T.num_slots;
     sc->wave_ok = T.wave_ok;
     sc->tree_ok = T.tree_ok;
     sc->path_ok = T.path_ok;
-    if (!deviceBvh) {
-        HIP_TRY(sc->nodes.upload(T.nodes)); HIP_TRY(sc->node_ext.upload(T.node_ext)); HIP_TRY(sc->tris.upload(T.tris));
-        HIP_TRY(sc->face_n.upload(T.face_n)); HIP_TRY(sc->face_uv.upload(T.face_uv)); HIP_TRY(sc->face_v12.upload(T.face_v12));
-    }
-    HIP_TRY(sc->objects.upload(T.objects)); HIP_TRY(sc->group_box.upload(T.group_box));
-    HIP_TRY(sc->materials.upload(T.materials)); HIP_TRY(sc->brdfs.upload(T.brdfs));
-    HIP_TRY(sc->textures.upload(T.textures)); HIP_TRY(sc->images.upload(T.images)); HIP_TRY(sc->texels.upload(T.texels));
-    HIP_TRY(sc->point_lights.upload(T.point_lights)); HIP_TRY(sc->area_lights.upload(T.area_lights));
-    HIP_TRY(sc->dir_lights.upload(T.dir_lights)); HIP_TRY(sc->spot_lights.upload(T.spot_lights));
-    HIP_TRY(sc->env_images.upload(T.env_images)); HIP_TRY(sc->env_mix.upload(T.env_mix));
-    HIP_TRY(sc->mesh_lights.upload(T.mesh_lights)); HIP_TRY(sc->light_faces.upload(T.light_faces));
-    HIP_TRY(sc->anodes.upload(T.anodes)); HIP_TRY(sc->ahtris.upload(T.ahtris)); HIP_TRY(sc->face_leaf.upload(T.face_leaf));
-    HIP_TRY(sc->perm.upload(T.perm)); HIP_TRY(sc->grad.upload(T.grad));
-    HIP_TRY(sc->counters.alloc(1));
-    HIP_TRY(hipMemset(sc->counters.p, 0, sizeof(rtg::DevCounters)));
-    HIP_TRY(sc->guard.alloc(1));
-    HIP_TRY(hipMemset(sc->guard.p, 0, sizeof(int)));
-
+    sc->max_depth = d->max_recursion_depth;
+    sc->cameras.assign(d->cameras, d->cameras + d->num_cameras);
+    const SceneGeom& g = *sc->geom;
     rtg::DevScene& S = sc->ds;
     std::memset(&S, 0, sizeof(S));
-    S.nodes = sc->nodes.p; S.node_ext = sc->node_ext.p; S.tris = sc->tris.p; S.face_n = sc->face_n.p;
-    S.face_uv = sc->face_uv.p;
-    S.face_v12 = sc->face_v12.p;
-    S.mesh_lights = sc->mesh_lights.p;
-    S.light_faces = sc->light_faces.p;
+    S.nodes = g.nodes.p; S.node_ext = g.node_ext.p; S.tris = g.tris.p; S.face_n = g.face_n.p;
+    S.face_uv = g.face_uv.p;
+    S.face_v12 = g.face_v12.p;
+    S.mesh_lights = sc->mesh_lights.ptr();
+    S.light_faces = g.light_faces.p;
     S.num_mesh = d->num_mesh_lights;
-    S.objects = sc->objects.p; S.group_box = sc->group_box.p; S.materials = sc->materials.p; S.brdfs = sc->brdfs.p;
-    S.textures = sc->textures.p; S.images = sc->images.p; S.texels = sc->texels.p;
-    S.point_lights = sc->point_lights.p; S.area_lights = sc->area_lights.p; S.dir_lights = sc->dir_lights.p;
-    S.spot_lights = sc->spot_lights.p; S.env_images = sc->env_images.p; S.env_mix = sc->env_mix.p;
-    S.perm = sc->perm.p; S.grad = sc->grad.p;
+    // (ptr(): null for an empty table, whether it never had entries or an update emptied it)
+    S.objects = sc->objects.ptr(); S.group_box = sc->group_box.ptr(); S.materials = sc->materials.ptr();
+    S.brdfs = sc->brdfs.ptr();
+    S.textures = sc->textures.ptr(); S.images = g.images.p; S.texels = g.texels.p;
+    S.point_lights = sc->point_lights.ptr(); S.area_lights = sc->area_lights.ptr(); S.dir_lights = sc->dir_lights.ptr();
+    S.spot_lights = sc->spot_lights.ptr(); S.env_images = sc->env_images.ptr();
+    S.env_mix = d->num_env_lights > 0 ? sc->env_mix->p : nullptr;
+    S.perm = g.perm.p; S.grad = g.grad.p;
     S.num_objects = d->num_objects; S.num_point = d->num_point_lights; S.num_area = d->num_area_lights;
     S.num_dir = d->num_dir_lights; S.num_spot = d->num_spot_lights; S.num_env = d->num_env_lights;
     S.max_depth = d->max_recursion_depth;
@@ -371,17 +420,35 @@ static int upload_tables(rtg_scene* sc, const rtg_scene_desc* d, const rtg::Scen
     S.ambient[0] = d->ambient_light.x; S.ambient[1] = d->ambient_light.y; S.ambient[2] = d->ambient_light.z;
     for (int k = 0; k < 3; ++k) S.background[k] = d->background[k];
     S.coop = (sc->feat & rtg::FEAT_BIGLEAF) ? 1 : 0;
-    S.anodes = sc->anodes.p;            // null without trees: DevBuf::upload of an empty table
-    S.ahtris = sc->ahtris.p;
+    S.anodes = g.anodes.p;              // null without trees: DevBuf::upload of an empty table
+    S.ahtris = g.ahtris.p;
     S.ahb_split = T.ahb_split;
-    S.face_leaf = sc->face_leaf.p;
+    S.face_leaf = g.face_leaf.p;
     S.guard = sc->guard.p;
     S.num_faces = (int)d->num_faces;
     S.num_textures = d->num_textures;
     S.num_images = d->num_images;
     S.num_materials = d->num_materials;
-    HIP_TRY(hipStreamCreateWithFlags(&sc->stream, hipStreamNonBlocking));
-    HIP_TRY(hipEventCreateWithFlags(&sc->done, hipEventDisableTiming));
+}
+
+// The tables to the device and the DevScene that points at them (the walk and face tables of
+// a device-built BVH are there already).
+static int upload_tables(rtg_scene* sc, const rtg_scene_desc* d, const rtg::SceneTables& T, bool deviceBvh) {
+    SceneGeom& g = *sc->geom;
+    g.node_count = T.node_count;
+    if (!deviceBvh) {
+        HIP_TRY(g.nodes.upload(T.nodes)); HIP_TRY(g.node_ext.upload(T.node_ext)); HIP_TRY(g.tris.upload(T.tris));
+        HIP_TRY(g.face_n.upload(T.face_n)); HIP_TRY(g.face_uv.upload(T.face_uv)); HIP_TRY(g.face_v12.upload(T.face_v12));
+    }
+    HIP_TRY(g.images.upload(T.images)); HIP_TRY(g.texels.upload(T.texels));
+    HIP_TRY(g.light_faces.upload(T.light_faces));
+    HIP_TRY(g.anodes.upload(T.anodes)); HIP_TRY(g.ahtris.upload(T.ahtris)); HIP_TRY(g.face_leaf.upload(T.face_leaf));
+    HIP_TRY(g.perm.upload(T.perm)); HIP_TRY(g.grad.upload(T.grad));
+    sc->env_mix = std::make_shared<DevBuf<unsigned long long>>();
+    HIP_TRY(sc->env_mix->upload(T.env_mix));
+    int rc = upload_mutable(sc, T);
+    if (rc) return rc;
+    scene_state(sc, d, T);
     HIP_TRY(hipDeviceSynchronize());
     return RTG_OK;
 }
@@ -403,20 +470,146 @@ int rtg_scene_create(const rtg_scene_desc* d, int device, rtg_scene** out) {
     std::unique_ptr<rtg_scene> sc(new (std::nothrow) rtg_scene);
     if (!sc) return set_err(RTG_ERR_NOMEM, "out of memory");
     sc->device = device;
-    sc->max_depth = d->max_recursion_depth;
-    sc->cameras.assign(d->cameras, d->cameras + d->num_cameras);
+    sc->geom = std::make_shared<SceneGeom>();
 
     const rtg::TableOptions opt = table_options();
     const bool deviceBvh = d->num_faces > 0 && d->num_nodes == 0;
     rtg::BvhReadback rb;
-    if (deviceBvh && (rc = build_bvh_on_device(sc.get(), d, opt.fast_shadow, rb))) return rc;
+    if (deviceBvh && (rc = build_bvh_on_device(sc->geom.get(), d, opt.fast_shadow, rb))) return rc;
 
     rtg::SceneTables T;
     rc = rtg::build_scene_tables(d, opt, deviceBvh ? &rb : nullptr, T, err);
     if (rc) return set_err(rc, "%s", err.c_str());
 
     if ((rc = upload_tables(sc.get(), d, T, deviceBvh))) return rc;
+    // for rtg_scene_update / rtg_scene_clone: the options, the kept state and the host copies of
+    // the mutable tables (the geometry's, by far the larger part, are dropped)
+    sc->opt = opt;
+    rtg::keep_tables(d, T, sc->kept);
+    for (auto* v : {&T.nodes, &T.tris, &T.face_n, &T.face_v12, &T.ahtris}) std::vector<float4>().swap(*v);
+    std::vector<int2>().swap(T.node_ext);
+    std::vector<float2>().swap(T.face_uv);
+    std::vector<float>().swap(T.texels);
+    std::vector<rtg::DevLightFace>().swap(T.light_faces);
+    std::vector<rtg::WNode>().swap(T.anodes);
+    std::vector<int>().swap(T.face_leaf);
+    sc->staged = std::move(T);
     *out = sc.release();
+    return RTG_OK;
+}
+
+// ---- scene updates (rtgpu.h: rtg_scene_update, rtg_scene_set_camera, rtg_scene_clone)
+int rtg_scene_update(rtg_scene* s, const rtg_scene_desc* d, void* stream) {
+    if (!s || !d) return set_err(RTG_ERR_INVALID, "null argument");
+    std::vector<rtg_scene*> reps(1, s);
+    reps.insert(reps.end(), s->replicas.begin(), s->replicas.end());
+    if (reps.size() > 1 && stream)
+        return set_err(RTG_ERR_INVALID, "a multi-device scene is updated synchronously (stream must be NULL)");
+    // every replica's tables first: nothing is changed unless all of them accept the description
+    std::vector<rtg::SceneTables> tables(reps.size());
+    try {
+        for (size_t i = 0; i < reps.size(); ++i) {
+            std::string err;
+            const int rc = rtg::update_scene_tables(d, reps[i]->kept, reps[i]->opt, tables[i], err);
+            if (rc) return set_err(rc, "%s", err.c_str());
+        }
+    } catch (const std::bad_alloc&) {
+        return set_err(RTG_ERR_NOMEM, "out of memory");
+    }
+    for (size_t i = 0; i < reps.size(); ++i) {
+        rtg_scene* r = reps[i];
+        hipStream_t st = (hipStream_t)stream;
+        HIP_TRY(hipSetDevice(r->device));
+        HIP_TRY(hipEventSynchronize(r->updated));       // the last update's copies read `staged`
+        r->staged = std::move(tables[i]);
+        const rtg::SceneTables& T = r->staged;
+        HIP_TRY(r->objects.update(T.objects, st)); HIP_TRY(r->group_box.update(T.group_box, st));
+        HIP_TRY(r->materials.update(T.materials, st)); HIP_TRY(r->brdfs.update(T.brdfs, st));
+        HIP_TRY(r->textures.update(T.textures, st));
+        HIP_TRY(r->point_lights.update(T.point_lights, st)); HIP_TRY(r->area_lights.update(T.area_lights, st));
+        HIP_TRY(r->dir_lights.update(T.dir_lights, st)); HIP_TRY(r->spot_lights.update(T.spot_lights, st));
+        HIP_TRY(r->env_images.update(T.env_images, st));
+        HIP_TRY(r->mesh_lights.update(T.mesh_lights, st));
+        // env_mix depends on the light's index alone: extended when there are more env lights
+        // than ever, into a buffer of this scene's own (clones may share the old one)
+        if (T.env_mix.size() > r->env_mix->n) {
+            auto grown = std::make_shared<DevBuf<unsigned long long>>();
+            HIP_TRY(grown->upload(T.env_mix));
+            r->env_mix = grown;
+        }
+        HIP_TRY(hipEventRecord(r->updated, st));
+        // rtg_render and the host-buffer queries run on the scene's own stream
+        HIP_TRY(hipStreamWaitEvent(r->stream, r->updated, 0));
+        scene_state(r, d, T);
+        if (reps.size() > 1) HIP_TRY(hipEventSynchronize(r->updated));
+    }
+    return RTG_OK;
+}
+
+int rtg_scene_set_camera(rtg_scene* s, int32_t index, const rtg_camera* cam) {
+    if (!s || !cam) return set_err(RTG_ERR_INVALID, "null argument");
+    if (index < 0 || index > (int32_t)s->cameras.size())
+        return set_err(RTG_ERR_INVALID, "camera index %d: the scene has %zu (index == count appends)", index,
+                       s->cameras.size());
+    std::vector<rtg_scene*> reps(1, s);
+    reps.insert(reps.end(), s->replicas.begin(), s->replicas.end());
+    for (rtg_scene* r : reps) {
+        if (index == (int32_t)r->cameras.size()) r->cameras.push_back(*cam);
+        else r->cameras[index] = *cam;
+    }
+    return RTG_OK;
+}
+
+int rtg_scene_num_cameras(const rtg_scene* s, int32_t* count) {
+    if (!s || !count) return set_err(RTG_ERR_INVALID, "null argument");
+    *count = (int32_t)s->cameras.size();
+    return RTG_OK;
+}
+
+int rtg_camera_setup(const rtg_camera_view* view, rtg_camera* cam) {
+    if (!view || !cam) return set_err(RTG_ERR_INVALID, "null argument");
+    rtg::camera_setup(*view, *cam);
+    return RTG_OK;
+}
+
+int rtg_scene_clone(const rtg_scene* src, rtg_scene** out) {
+    if (!src || !out) return set_err(RTG_ERR_INVALID, "null argument");
+    *out = nullptr;
+    if (!src->replicas.empty()) return set_err(RTG_ERR_INVALID, "a multi-device scene cannot be cloned");
+    HIP_TRY(hipSetDevice(src->device));
+    std::unique_ptr<rtg_scene> sc(new (std::nothrow) rtg_scene);
+    if (!sc) return set_err(RTG_ERR_NOMEM, "out of memory");
+    sc->device = src->device;
+    sc->geom = src->geom;
+    sc->env_mix = src->env_mix;
+    sc->opt = src->opt;
+    try {
+        sc->kept = src->kept;
+        sc->staged = src->staged;       // the source's tables in effect (read-only for its copies in flight)
+        sc->cameras = src->cameras;
+    } catch (const std::bad_alloc&) {
+        return set_err(RTG_ERR_NOMEM, "out of memory");
+    }
+    if (int rc = upload_mutable(sc.get(), sc->staged)) return rc;
+    sc->feat = src->feat; sc->shade_sk = src->shade_sk; sc->num_slots = src->num_slots;
+    sc->wave_ok = src->wave_ok; sc->tree_ok = src->tree_ok; sc->path_ok = src->path_ok;
+    sc->max_depth = src->max_depth;
+    // the source's DevScene over the clone's own tables (pointers where the source has entries)
+    rtg::DevScene& S = sc->ds;
+    S = src->ds;
+    S.objects = sc->objects.ptr(); S.group_box = sc->group_box.ptr(); S.materials = sc->materials.ptr();
+    S.brdfs = sc->brdfs.ptr(); S.textures = sc->textures.ptr();
+    S.point_lights = sc->point_lights.ptr(); S.area_lights = sc->area_lights.ptr(); S.dir_lights = sc->dir_lights.ptr();
+    S.spot_lights = sc->spot_lights.ptr(); S.env_images = sc->env_images.ptr(); S.mesh_lights = sc->mesh_lights.ptr();
+    S.guard = sc->guard.p;
+    HIP_TRY(hipDeviceSynchronize());
+    *out = sc.release();
+    return RTG_OK;
+}
+
+int rtg_scene_shares_geometry(const rtg_scene* a, const rtg_scene* b, int32_t* yes) {
+    if (!a || !b || !yes) return set_err(RTG_ERR_INVALID, "null argument");
+    *yes = a->geom == b->geom ? 1 : 0;
     return RTG_OK;
 }
 
@@ -788,8 +981,16 @@ static int launch(rtg_scene* s, const rtg_render_opts* o, const rtg::DevCamera& 
         int rc = ensure_wave(ww, entries, s->num_slots, blocks, one_payload(s), P.slabs > 1);
         if (rc) return rc;
 
+        // the shadow-ray layout is the scene's as it is now: buffers sized for another one (before
+        // an rtg_scene_update changed the lights) only have room to spare
+        auto layout_now = [&](rtg::WaveBufs& B) {
+            const int pay = one_payload(s);
+            B.num_slots = s->num_slots;
+            B.pay3 = pay == 3;
+            if (!pay) B.q_pay = nullptr;
+        };
         rtg::WaveBufs W = ww.W;
-        W.num_slots = s->num_slots;
+        layout_now(W);
         if (P.accum_only) W.accum = (float4*)d_accum;
         else if (C.spp > 1) {   // internal accumulator indexed by absolute pixel
             size_t need = (size_t)C.width * C.height;
@@ -797,7 +998,7 @@ static int launch(rtg_scene* s, const rtg_render_opts* o, const rtg::DevCamera& 
                 int rc2 = ensure_wave(ww, need, s->num_slots, blocks, one_payload(s), P.slabs > 1);
                 if (rc2) return rc2;
                 W = ww.W;
-                W.num_slots = s->num_slots;
+                layout_now(W);
             }
         }
         if ((s->feat & rtg::FEAT_BIGLEAF) && !stats && rtg::defer_leaves()) {

@@ -332,21 +332,26 @@ void scene_scalars(const rtg_scene_desc* d, const TableOptions& opt, int feat, b
     T.shade_sk = sk;
 }
 
-// Mesh lights (meshLight.h): their faces in MeshLight::faces order (the BVH-permuted one;
+// A mesh light's record (meshLight.h) over faces [face_begin, ...) of light_faces.
+void mesh_light_record(const rtg_scene_desc* d, int i, int face_begin, DevMeshLight& L) {
+    const rtg_object& o = d->objects[d->mesh_lights[i].object];
+    const rtg_mesh& M = d->meshes[o.mesh];
+    std::memset(&L, 0, sizeof(L));
+    L.id = o.id;
+    L.face_begin = face_begin;
+    L.face_count = M.face_count;
+    f4(L.radiance, d->mesh_lights[i].radiance);
+    L.surface_area = M.surface_area;
+    for (int k = 0; k < 12; ++k) L.xf[k] = o.transform[k];
+}
+
+// Mesh lights: their records and their faces in MeshLight::faces order (the BVH-permuted one;
 // `perm`, nullable: final face position -> description face).
 void mesh_light_tables(const rtg_scene_desc* d, const std::vector<int>* perm, SceneTables& T) {
     T.mesh_lights.resize(d->num_mesh_lights);
     for (int i = 0; i < d->num_mesh_lights; ++i) {
-        const rtg_object& o = d->objects[d->mesh_lights[i].object];
-        const rtg_mesh& M = d->meshes[o.mesh];
-        DevMeshLight& L = T.mesh_lights[i];
-        std::memset(&L, 0, sizeof(L));
-        L.id = o.id;
-        L.face_begin = (int)T.light_faces.size();
-        L.face_count = M.face_count;
-        f4(L.radiance, d->mesh_lights[i].radiance);
-        L.surface_area = M.surface_area;
-        for (int k = 0; k < 12; ++k) L.xf[k] = o.transform[k];
+        mesh_light_record(d, i, (int)T.light_faces.size(), T.mesh_lights[i]);
+        const rtg_mesh& M = d->meshes[d->objects[d->mesh_lights[i].object].mesh];
         for (int f = 0; f < M.face_count; ++f) {
             const rtg_face& F = d->faces[perm ? (*perm)[M.face_offset + f] : M.face_offset + f];
             DevLightFace lf;
@@ -358,8 +363,8 @@ void mesh_light_tables(const rtg_scene_desc* d, const std::vector<int>* perm, Sc
     }
 }
 
-// Materials, BRDFs, textures and the texel pool.
-void shading_tables(const rtg_scene_desc* d, SceneTables& T) {
+// Materials, BRDFs and textures.
+void shading_records(const rtg_scene_desc* d, SceneTables& T) {
     T.materials.resize(d->num_materials);
     for (int i = 0; i < d->num_materials; ++i) {
         const rtg_material& m = d->materials[i];
@@ -397,15 +402,24 @@ void shading_tables(const rtg_scene_desc* d, SceneTables& T) {
         X.normalizer = t.normalizer;
         X.noise_abs = t.noise_abs;
     }
+}
+
+// An image's record at `offset` of the texel pool.
+void image_record(const rtg_image& im, long long offset, DevImage& I) {
+    std::memset(&I, 0, sizeof(I));
+    I.width = im.width; I.height = im.height; I.channels = im.channels;
+    I.offset = offset;
+}
+
+// The records above, the texel pool and the Perlin tables.
+void shading_tables(const rtg_scene_desc* d, SceneTables& T) {
+    shading_records(d, T);
     // texel pool; each image padded with one extra row + 4 floats so the reference's
     // edge reads (bilinear p+1, 1-channel RGB reads) stay inside the allocation
     T.images.resize(d->num_images);
     for (int i = 0; i < d->num_images; ++i) {
         const rtg_image& im = d->images[i];
-        DevImage& I = T.images[i];
-        std::memset(&I, 0, sizeof(I));
-        I.width = im.width; I.height = im.height; I.channels = im.channels;
-        I.offset = (long long)T.texels.size();
+        image_record(im, (long long)T.texels.size(), T.images[i]);
         size_t n = (size_t)im.width * im.height * im.channels;
         T.texels.insert(T.texels.end(), im.texels, im.texels + n);
         T.texels.insert(T.texels.end(), (size_t)im.width * im.channels + 4, 0.f);
@@ -476,9 +490,11 @@ bool any_mapped(const rtg_scene_desc* d) {
     return false;
 }
 
-int validate_desc(const rtg_scene_desc* d, std::string& err) {
+namespace {
+// validate_desc; `geometry` false: without the checks that read faces, nodes or texels
+int validate(const rtg_scene_desc* d, bool geometry, std::string& err) {
     // the packet walks address records by 32-bit byte offsets (rtg_common.hpp rec_at)
-    if (d->num_faces > ((int64_t)1 << 25))
+    if (geometry && d->num_faces > ((int64_t)1 << 25))
         return fail(err, RTG_ERR_INVALID, "%lld faces: at most 2^25 per scene", (long long)d->num_faces);
     for (int i = 0; i < d->num_mesh_lights; ++i) {
         const int o = d->mesh_lights ? d->mesh_lights[i].object : -1;
@@ -505,10 +521,10 @@ int validate_desc(const rtg_scene_desc* d, std::string& err) {
         if (o.kind != RTG_OBJ_SPHERE && (o.mesh < 0 || o.mesh >= d->num_meshes))
             return fail(err, RTG_ERR_INVALID, "object %d: bad mesh", i);
     }
-    for (int i = 0; i < d->num_images; ++i)
+    for (int i = 0; i < d->num_images && geometry; ++i)
         if (d->images[i].channels < 1 || !d->images[i].texels) return fail(err, RTG_ERR_INVALID, "image %d: no texels", i);
     std::vector<int> order;
-    for (int m = 0; m < d->num_meshes && d->num_nodes > 0; ++m)
+    for (int m = 0; m < d->num_meshes && d->num_nodes > 0 && geometry; ++m)
         if (!mesh_preorder(d->meshes[m], d->nodes + d->meshes[m].node_offset, order))
             return fail(err, RTG_ERR_INVALID, "mesh %d: corrupt BVH", m);
     for (int i = 0; i < d->num_env_lights; ++i)
@@ -516,6 +532,10 @@ int validate_desc(const rtg_scene_desc* d, std::string& err) {
             return fail(err, RTG_ERR_INVALID, "env light %d: bad image", i);
     return RTG_OK;
 }
+}  // namespace
+
+int validate_desc(const rtg_scene_desc* d, std::string& err) { return validate(d, true, err); }
+int validate_desc_update(const rtg_scene_desc* d, std::string& err) { return validate(d, false, err); }
 
 int build_scene_tables(const rtg_scene_desc* d, const TableOptions& opt, const BvhReadback* rb, SceneTables& T,
                        std::string& err) {
@@ -541,10 +561,95 @@ int build_scene_tables(const rtg_scene_desc* d, const TableOptions& opt, const B
     if (opt.fast_shadow && d->num_meshes > 0)
         shadow_tables(d, opt, rb ? rb->nodes : T.nodes, rb ? rb->ext : T.node_ext, rb ? rb->tris.data() : T.tris.data(), T);
     T.ahb_split = T.ahb_mode == AHB_SPLIT && !T.anodes.empty();
+    T.bigleaf = bigleaf;
     instance_groups(T);
     scene_scalars(d, opt, feat, bigleaf, T);
     mesh_light_tables(d, rb ? &rb->perm : nullptr, T);
     shading_tables(d, T);
+    light_tables(d, T);
+    return RTG_OK;
+}
+
+void keep_tables(const rtg_scene_desc* d, const SceneTables& T, KeptTables& K) {
+    K = KeptTables();
+    K.mesh_begin = T.mesh_begin; K.mesh_end = T.mesh_end; K.aroot = T.aroot;
+    K.bigleaf = T.bigleaf;
+    K.ahb_mode = T.ahb_mode; K.ahb_ok = T.ahb_ok; K.ahb_split = T.ahb_split;
+    K.has_uv = any_uv(d); K.has_v12 = any_mapped(d);
+    for (int i = 0; i < d->num_mesh_lights; ++i) {
+        K.light_face_begin.push_back(T.mesh_lights[i].face_begin);
+        K.light_face_count.push_back(T.mesh_lights[i].face_count);
+        K.light_object.push_back(d->mesh_lights[i].object);
+    }
+    for (const DevImage& I : T.images) K.image_offset.push_back(I.offset);
+    K.num_faces = d->num_faces; K.num_nodes = d->num_nodes;
+    for (int m = 0; m < d->num_meshes; ++m) {
+        const rtg_mesh& M = d->meshes[m];
+        K.meshes.push_back({M.face_offset, M.face_count, M.node_offset, M.node_count, M.has_uv});
+    }
+    for (int i = 0; i < d->num_objects; ++i) K.objects.push_back(make_int2(d->objects[i].kind, d->objects[i].mesh));
+    for (int i = 0; i < d->num_images; ++i)
+        K.images.push_back({d->images[i].width, d->images[i].height, d->images[i].channels, d->images[i].is_hdr});
+}
+
+int same_geometry(const rtg_scene_desc* d, const KeptTables& K, std::string& err) {
+    if (d->num_meshes != (int)K.meshes.size() || d->num_faces != K.num_faces || d->num_nodes != K.num_nodes ||
+        d->num_objects != (int)K.objects.size())
+        return fail(err, RTG_ERR_INVALID, "geometry differs: %d meshes, %lld faces, %lld nodes, %d objects against the "
+                    "scene's %zu, %lld, %lld, %zu", d->num_meshes, (long long)d->num_faces, (long long)d->num_nodes,
+                    d->num_objects, K.meshes.size(), K.num_faces, K.num_nodes, K.objects.size());
+    if ((d->num_meshes > 0 && !d->meshes) || (d->num_objects > 0 && !d->objects) || (d->num_images > 0 && !d->images) ||
+        (d->num_mesh_lights > 0 && !d->mesh_lights))
+        return fail(err, RTG_ERR_INVALID, "null table in the description");
+    for (int m = 0; m < d->num_meshes; ++m) {
+        const rtg_mesh& M = d->meshes[m];
+        const KeptTables::Mesh& k = K.meshes[m];
+        if (M.face_offset != k.face_offset || M.face_count != k.face_count || M.node_offset != k.node_offset ||
+            M.node_count != k.node_count || M.has_uv != k.has_uv)
+            return fail(err, RTG_ERR_INVALID, "mesh %d: face / node range or UVs differ from the scene's", m);
+    }
+    for (int i = 0; i < d->num_objects; ++i)
+        if (d->objects[i].kind != K.objects[i].x || d->objects[i].mesh != K.objects[i].y)
+            return fail(err, RTG_ERR_INVALID, "object %d: kind or mesh differs from the scene's", i);
+    if (d->num_images != (int)K.images.size())
+        return fail(err, RTG_ERR_INVALID, "%d images, the scene has %zu", d->num_images, K.images.size());
+    for (int i = 0; i < d->num_images; ++i) {
+        const rtg_image& im = d->images[i];
+        const KeptTables::Image& k = K.images[i];
+        if (im.width != k.width || im.height != k.height || im.channels != k.channels || im.is_hdr != k.is_hdr)
+            return fail(err, RTG_ERR_INVALID, "image %d: size or format differs from the scene's", i);
+    }
+    if (d->num_mesh_lights != (int)K.light_object.size())
+        return fail(err, RTG_ERR_INVALID, "%d mesh lights, the scene has %zu", d->num_mesh_lights, K.light_object.size());
+    for (int i = 0; i < d->num_mesh_lights; ++i)
+        if (d->mesh_lights[i].object != K.light_object[i])
+            return fail(err, RTG_ERR_INVALID, "mesh light %d: object differs from the scene's", i);
+    return RTG_OK;
+}
+
+int update_scene_tables(const rtg_scene_desc* d, const KeptTables& K, const TableOptions& opt, SceneTables& T,
+                        std::string& err) {
+    int rc = same_geometry(d, K, err);
+    if (!rc) rc = validate_desc_update(d, err);
+    if (rc) return rc;
+    if (any_mapped(d) && !K.has_v12)
+        return fail(err, RTG_ERR_UNSUPPORTED, "a normal / bump map in a scene created without one (no face_v12 table)");
+    if (K.ahb_split)
+        return fail(err, RTG_ERR_UNSUPPORTED, "any-hit trees built in the split mode depend on transforms and lights");
+    T = SceneTables();
+    T.mesh_begin = K.mesh_begin; T.mesh_end = K.mesh_end; T.aroot = K.aroot;
+    T.ahb_mode = K.ahb_mode; T.ahb_ok = K.ahb_ok; T.ahb_split = K.ahb_split; T.bigleaf = K.bigleaf;
+    const int feat = object_table(d, T);
+    if (!T.aroot.empty())
+        for (int i = 0; i < d->num_objects; ++i)
+            T.objects[i].aroot = d->objects[i].kind != RTG_OBJ_SPHERE ? T.aroot[d->objects[i].mesh] : -1;
+    instance_groups(T);
+    scene_scalars(d, opt, feat, K.bigleaf, T);
+    T.mesh_lights.resize(d->num_mesh_lights);
+    for (int i = 0; i < d->num_mesh_lights; ++i) mesh_light_record(d, i, K.light_face_begin[i], T.mesh_lights[i]);
+    shading_records(d, T);
+    T.images.resize(d->num_images);
+    for (int i = 0; i < d->num_images; ++i) image_record(d->images[i], K.image_offset[i], T.images[i]);
     light_tables(d, T);
     return RTG_OK;
 }

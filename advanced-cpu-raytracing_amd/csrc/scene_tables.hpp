@@ -66,7 +66,27 @@ struct SceneTables {
     int ahb_mode = AHB_EXACT;       // the mode the any-hit trees were built in
     bool ahb_split = false;
     bool ahb_ok = true;             // false: a leaf range exceeded the trees' encoding (no trees built)
+    bool bigleaf = false;           // a leaf of more than kBigLeaf faces (FEAT_BIGLEAF with TableOptions::coop)
     AhbStats ahb;
+};
+
+// What a scene keeps of its creation for update_scene_tables: the results of the geometry's
+// processing that the mutable tables refer to, and the signature a later description must match
+// (rtgpu.h, rtg_scene_update's same-geometry contract).
+struct KeptTables {
+    std::vector<int> mesh_begin, mesh_end, aroot;   // aroot empty: no any-hit trees were asked for
+    bool bigleaf = false;
+    int ahb_mode = AHB_EXACT;
+    bool ahb_ok = true, ahb_split = false;
+    bool has_uv = false, has_v12 = false;           // face_uv / face_v12 exist (any_uv / any_mapped at creation)
+    std::vector<int> light_face_begin, light_face_count, light_object;   // per mesh light
+    std::vector<long long> image_offset;            // per image, into the texel pool
+    struct Mesh { int face_offset, face_count, node_offset, node_count, has_uv; };
+    struct Image { int width, height, channels, is_hdr; };
+    long long num_faces = 0, num_nodes = 0;
+    std::vector<Mesh> meshes;
+    std::vector<int2> objects;                      // kind, mesh
+    std::vector<Image> images;
 };
 
 // scenes with UVs carry face_uv, scenes with a normal / bump map in effect face_v12
@@ -75,9 +95,27 @@ bool any_mapped(const rtg_scene_desc* d);
 
 // Every check on a description; RTG_OK or the code, with the message in `err`.
 int validate_desc(const rtg_scene_desc* d, std::string& err);
+// The same without the checks that read geometry (face count, BVH links, texels): what an update
+// re-checks.  The description's meshes[] and the objects' mesh indices must be valid already.
+int validate_desc_update(const rtg_scene_desc* d, std::string& err);
 
 // `rb` null: the description's own BVH, re-laid in pre-order.
 int build_scene_tables(const rtg_scene_desc* d, const TableOptions& opt, const BvhReadback* rb, SceneTables& T,
                        std::string& err);
+
+// The kept state of tables just built from `d`.
+void keep_tables(const rtg_scene_desc* d, const SceneTables& T, KeptTables& K);
+// RTG_OK when `d` matches the signature in K, else RTG_ERR_INVALID with the first difference.
+int same_geometry(const rtg_scene_desc* d, const KeptTables& K, std::string& err);
+// The mutable tables and scalars of `d` over the geometry K was kept from: objects, group_box,
+// materials, brdfs, textures, the image records, the four analytic light arrays, env_images,
+// env_mix, the mesh-light records, feat, shade_sk, num_slots, wave_ok, tree_ok, path_ok (and
+// mesh_begin / mesh_end / aroot / the ahb_* flags, copied from K) -- each equal, byte for byte, to
+// build_scene_tables(d)'s; every other table of T is left empty.  Reads neither d->faces, d->nodes
+// nor any texel.  `opt`: the options of the creation.  Checks same_geometry and
+// validate_desc_update first; RTG_ERR_UNSUPPORTED for a map that needs face_v12 where K has none
+// and for split any-hit trees.
+int update_scene_tables(const rtg_scene_desc* d, const KeptTables& K, const TableOptions& opt, SceneTables& T,
+                        std::string& err);
 
 }  // namespace rtg

@@ -66,6 +66,59 @@ class _Camera(ctypes.Structure):
                 ("tm_burn", ctypes.c_float), ("tm_saturation", ctypes.c_float), ("tm_gamma", ctypes.c_float)]
 
 
+class CameraView(ctypes.Structure):
+    """rtg_camera_view (72 B): what a <Camera> element states about the view."""
+    _fields_ = [("position", ctypes.c_float * 3), ("gaze", ctypes.c_float * 3), ("up", ctypes.c_float * 3),
+                ("look_at", ctypes.c_int32), ("near_plane", ctypes.c_float * 4), ("fov_y", ctypes.c_float),
+                ("near_dist", ctypes.c_float), ("width", ctypes.c_int32), ("height", ctypes.c_int32)]
+
+
+class Camera:
+    """One rtg_camera by value (RTG_CAMERA_SIZE bytes): what HostScene.camera_record() and
+    camera_setup() return and DeviceScene.set_camera() takes."""
+
+    def __init__(self, raw: bytes = b""):
+        self.buf = ctypes.create_string_buffer(bytes(raw).ljust(RTG_CAMERA_SIZE, b"\0"), RTG_CAMERA_SIZE)
+
+    @property
+    def head(self) -> "_Camera":
+        return _Camera.from_buffer(self.buf)
+
+    @property
+    def width(self) -> int:
+        return self.head.width
+
+    @property
+    def height(self) -> int:
+        return self.head.height
+
+    def view_bytes(self) -> bytes:
+        """The fields rtg_camera_setup fills: position .. q, the extents and near distance, the size."""
+        return self.buf.raw[:88]
+
+    def copy(self) -> "Camera":
+        return Camera(self.buf.raw)
+
+
+def camera_setup(position, gaze, up, near_dist, width, height, near_plane=None, fov_y=None, base: Camera = None) -> Camera:
+    """rtg_camera_setup (host only): the camera of a view.  ``fov_y`` (degrees) selects the lookAt
+    form, where ``gaze`` is the gaze point; otherwise ``gaze`` is a direction and ``near_plane`` =
+    (left, right, bottom, top).  ``base``: the camera whose other fields (samples, lens,
+    tonemapper, renderer flags) the result keeps; default a one-sample camera."""
+    v = CameraView()
+    v.position[:], v.gaze[:], v.up[:] = position, gaze, up
+    v.look_at = 1 if fov_y is not None else 0
+    if near_plane is not None:
+        v.near_plane[:] = near_plane
+    v.fov_y = fov_y if fov_y is not None else 0.0
+    v.near_dist, v.width, v.height = near_dist, width, height
+    cam = base.copy() if base is not None else Camera()
+    if base is None:
+        cam.head.spp = 1
+    _check(lib().rtg_camera_setup(ctypes.byref(v), ctypes.addressof(cam.buf)))
+    return cam
+
+
 class _DescHead(ctypes.Structure):
     """Head of rtg_scene_desc (include/rtgpu.h) up to the camera list."""
     _fields_ = [("background", ctypes.c_int32 * 3), ("shadow_epsilon", ctypes.c_float),
@@ -125,6 +178,8 @@ EXPORTED = [
     "rtg_trace_rays_device", "rtg_trace_rays", "rtg_camera_rays_device", "rtg_camera_rays", "rtg_desc_trace_rays",
     "rtg_radiance_rays_device", "rtg_radiance_rays",
     "rtg_surface_rays_device", "rtg_surface_rays",
+    "rtg_scene_update", "rtg_scene_set_camera", "rtg_scene_num_cameras", "rtg_camera_setup",
+    "rtg_scene_clone", "rtg_scene_shares_geometry",
 ]
 
 _lib = None
@@ -192,6 +247,12 @@ def lib() -> ctypes.CDLL:
     L.rtg_radiance_rays.argtypes = [vp, P(RadianceOpts), vp, vp, ctypes.c_int64, vp]
     L.rtg_surface_rays_device.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_uint32, vp, vp]
     L.rtg_surface_rays.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_uint32, vp]
+    L.rtg_scene_update.argtypes = [vp, vp, vp]
+    L.rtg_scene_set_camera.argtypes = [vp, i32, vp]
+    L.rtg_scene_num_cameras.argtypes = [vp, P(i32)]
+    L.rtg_camera_setup.argtypes = [P(CameraView), vp]
+    L.rtg_scene_clone.argtypes = [vp, P(vp)]
+    L.rtg_scene_shares_geometry.argtypes = [vp, vp, P(i32)]
     _lib = L
     return L
 
@@ -263,6 +324,13 @@ class HostScene:
             return None
         return (cam.tm_key, cam.tm_burn, cam.tm_saturation, cam.tm_gamma)
 
+    def camera_record(self, idx: int = 0) -> Camera:
+        """Camera idx's rtg_camera by value (for DeviceScene.set_camera, or as camera_setup's base)."""
+        head = _DescHead.from_address(self.desc)
+        if not 0 <= idx < head.num_cameras:
+            raise RTGError(-1, "camera index out of range")
+        return Camera(ctypes.string_at(head.cameras + idx * RTG_CAMERA_SIZE, RTG_CAMERA_SIZE))
+
     def counts(self) -> dict:
         v = [ctypes.c_int64() for _ in range(4)]
         _check(lib().rtg_desc_counts(self.desc, *[ctypes.byref(x) for x in v]))
@@ -321,6 +389,51 @@ class DeviceScene:
         self.host = host
         self.device = device
         self.devices = list(devices) if devices else [device]
+        self._cams = {}     # cameras set by set_camera since the last update: index -> size
+
+    def _camera(self, idx: int) -> dict:
+        """Width and height of the scene's camera idx: set_camera's, else the description's."""
+        return self._cams[idx] if idx in self._cams else self.host.camera(idx)
+
+    def update(self, host: HostScene, stream: int = 0):
+        """rtg_scene_update: every non-geometric part of the scene -- cameras, lights, materials,
+        textures' records, object transforms, the global scalars -- replaced in place by
+        ``host``'s, over the geometry as uploaded; afterwards every render and query answers bit
+        for bit as a scene freshly created from ``host``.  ``host`` must describe the same
+        geometry (meshes, face and node ranges, object kinds, images' sizes, mesh lights'
+        objects), else RTGError -1 and nothing changes; -6 for a map that needs a table the scene
+        was created without, or split any-hit trees.  The copies are enqueued on ``stream``
+        (0 = default): work enqueued there before sees the old scene, work after it the new one."""
+        _check(lib().rtg_scene_update(self._s, host.desc, stream or None))
+        self.host = host
+        self._cams = {}
+
+    def set_camera(self, index: int, cam: Camera):
+        """rtg_scene_set_camera: replace camera ``index`` (``index == num_cameras()`` appends) by
+        ``cam`` (HostScene.camera_record / camera_setup).  No device memory is touched."""
+        _check(lib().rtg_scene_set_camera(self._s, index, ctypes.addressof(cam.buf)))
+        self._cams[index] = {"width": cam.width, "height": cam.height, "spp": cam.head.spp,
+                             "tonemapped": bool(cam.head.has_tonemapper)}
+
+    def num_cameras(self) -> int:
+        n = ctypes.c_int32()
+        _check(lib().rtg_scene_num_cameras(self._s, ctypes.byref(n)))
+        return n.value
+
+    def clone(self) -> "DeviceScene":
+        """rtg_scene_clone: a second scene on the same device that shares this one's geometry
+        buffers and owns what update() writes -- one clone per frame in flight.  Either may be
+        closed first."""
+        s = ctypes.c_void_p()
+        _check(lib().rtg_scene_clone(self._s, ctypes.byref(s)))
+        c = DeviceScene.__new__(DeviceScene)
+        c._s, c.host, c.device, c.devices, c._cams = s, self.host, self.device, [self.device], dict(self._cams)
+        return c
+
+    def shares_geometry(self, other: "DeviceScene") -> bool:
+        yes = ctypes.c_int32()
+        _check(lib().rtg_scene_shares_geometry(self._s, other._s, ctypes.byref(yes)))
+        return bool(yes.value)
 
     @staticmethod
     def opts(camera=0, sample_begin=0, sample_count=-1, rows=(0, 0), flags=0, seed=0x5EED, part=(0, 1)) -> RenderOpts:
@@ -330,7 +443,7 @@ class DeviceScene:
         """Host-buffer render of one camera -> (hdr float32 HxWx3, ldr uint8 HxWx3).  With
         ``part=(i, n)`` only part i's rows are rendered and written (zeros elsewhere, or
         what ``out=(hdr, ldr)`` already holds)."""
-        c = self.host.camera(camera)
+        c = self._camera(camera)
         if out is None:
             hdr = np.zeros((c["height"], c["width"], 3), np.float32)
             ldr = np.zeros((c["height"], c["width"], 3), np.uint8)
@@ -378,7 +491,7 @@ class DeviceScene:
         """The rays render() traces for ``camera`` at sample index ``sample`` and ``seed``, rows
         ``rows`` in pixel order (rtg_camera_rays): RAY_DTYPE array, tmax = inf, time = the
         motion-blur draw."""
-        c = self.host.camera(camera)
+        c = self._camera(camera)
         r0 = max(rows[0], 0)
         r1 = c["height"] if rows[1] <= 0 or rows[1] > c["height"] else rows[1]
         rays = np.zeros(max(r1 - r0, 0) * c["width"], RAY_DTYPE)

@@ -591,6 +591,81 @@ int rtg_radiance_rays(rtg_scene* scene, const rtg_radiance_opts* opts, const rtg
                       const int32_t* pixel_ids, int64_t n, float* rgbt);
 
 /* ------------------------------------------------------------------------- */
+/* Scene updates: cameras, lights, materials and object transforms of a live  */
+/* scene replaced in place, over geometry that stays as uploaded.  Added      */
+/* symbols and one type only -- RTG_ABI_VERSION stays 6.                      */
+/* ------------------------------------------------------------------------- */
+/* Replaces every non-geometric part of `scene` by `desc`'s: the cameras (their count may change);
+ * background, bg_texture, shadow_epsilon, max_recursion_depth, ambient_light; materials, BRDFs and
+ * texture records; all six light arrays (their counts may change); and per object the transforms,
+ * boxes, flags, material, texture slots, motion-blur vector, sphere centre and radius, and id.
+ *
+ * Guarantee: afterwards rtg_render*, rtg_trace_rays*, rtg_camera_rays*, rtg_surface_rays* and
+ * rtg_radiance_rays* behave bit for bit as on a scene freshly created from `desc` (with the
+ * environment knobs the scene was created under).  No BVH is walked or built, no any-hit tree
+ * rebuilt, no texel uploaded: the device side is a handful of small copies into existing tables.
+ *
+ * Same-geometry contract, checked before anything is changed; a mismatch is RTG_ERR_INVALID and
+ * leaves the scene untouched.  Against the description the scene was created from:
+ *  - num_meshes, num_faces, num_nodes, num_objects equal; per mesh face_offset, face_count,
+ *    node_offset, node_count, has_uv equal; per object kind and mesh equal;
+ *  - num_images equal, and per image width, height, channels, is_hdr;
+ *  - num_mesh_lights equal, and each mesh_lights[i].object.
+ * desc->faces, desc->nodes and images[].texels are never read (they may be NULL): face data, BVH,
+ * any-hit trees, the mesh lights' faces and the texel pool stay as uploaded, and the caller
+ * promises they still match.  Vertex edits need a new scene.
+ *
+ * Refused with RTG_ERR_UNSUPPORTED, scene untouched:
+ *  - `desc` needs a table the scene was created without: the faces' raw vertices exist only if
+ *    some object had a normal or bump map in effect at creation, so a map newly attached in a
+ *    scene that had none is refused;
+ *  - the scene's any-hit trees were built in the split mode (RTG_AHB=split): their padding
+ *    depends on the transforms and lights;
+ *  - max_recursion_depth above the kernels' bound.
+ * The other checks of rtg_scene_create that do not concern geometry apply with their codes; a null
+ * argument is RTG_ERR_INVALID.
+ *
+ * Ordering: the copies are enqueued on `stream` (a hipStream_t, NULL = default stream), like
+ * rtg_render_device's work.  Work enqueued on that stream before the call sees the old tables,
+ * work enqueued after it the new ones; the scene's own stream (rtg_render and the host-buffer
+ * queries) waits for the copies too.  Work of this scene in flight on any other stream during the
+ * call races with it: that is the caller's to order.  Host-side state (cameras, counts, pipeline
+ * choice) switches at the call.  A table that outgrows its capacity (more lights, materials or
+ * textures than ever before) is reallocated, which waits for the device.  On a multi-device scene
+ * every replica is updated synchronously and a non-NULL `stream` is RTG_ERR_INVALID.  A HIP error
+ * part-way (RTG_ERR_HIP / RTG_ERR_NOMEM) leaves the scene unusable. */
+int rtg_scene_update(rtg_scene* scene, const rtg_scene_desc* desc, void* stream);
+
+/* Cameras without a description.  rtg_scene_set_camera replaces camera `index`, or appends with
+ * index == the count; it touches no device memory (cameras travel to the kernels by value) and
+ * sets every replica of a multi-device scene.  A camera with a non-positive size is accepted: the
+ * queries take it, the renders refuse it. */
+int rtg_scene_set_camera(rtg_scene* scene, int32_t index, const rtg_camera* cam);
+int rtg_scene_num_cameras(const rtg_scene* scene, int32_t* count);
+typedef struct {
+    rtg_float3 position, gaze, up;     /* gaze: direction, or the gaze point with look_at */
+    int32_t look_at;
+    float near_plane[4];               /* left right bottom top; ignored with look_at */
+    float fov_y;                       /* degrees; look_at only */
+    float near_dist;
+    int32_t width, height;
+} rtg_camera_view;
+/* Host only: Camera::SetupDefault / SetupLookAt (camera.cpp:5-72) -- the loader's own arithmetic,
+ * so a camera set up here from a <Camera>'s numbers equals the loaded one bit for bit.  Fills
+ * position, gaze, up, right, q, left, right_ext, bottom, top, near_dist, width and height of *cam
+ * and leaves its other fields (samples, lens, tonemapper, renderer flags, name) as they are. */
+int rtg_camera_setup(const rtg_camera_view* view, rtg_camera* cam);
+
+/* A second scene on the same device over the source's geometry: the clone shares the immutable
+ * buffers (BVH, faces, any-hit trees, mesh-light faces, texel pool and image records, noise
+ * tables) by reference count and owns everything rtg_scene_update may write (objects, materials,
+ * textures, lights, cameras) as well as its stream, work buffers, plans, counters and scratch.
+ * One clone per frame in flight, each updated to its own state, animates over one copy of the
+ * geometry.  Either scene may be destroyed first.  A multi-device source is RTG_ERR_INVALID. */
+int rtg_scene_clone(const rtg_scene* scene, rtg_scene** out);
+int rtg_scene_shares_geometry(const rtg_scene* a, const rtg_scene* b, int32_t* yes);
+
+/* ------------------------------------------------------------------------- */
 /* Tonemapping (tonemapper.h, main.cpp:187-192)                               */
 /* ------------------------------------------------------------------------- */
 /* Tonemapper(opType, keyValue, burnPerct, saturation, gamma) (tonemapper.h:18-25);

@@ -13,7 +13,7 @@ renders: RTG_FRAME_KERNEL=0 splits the sample pass into k_primary + k_shade_shad
 RTG_RENDER_EXACT_SHADOW gives k_shadow with the reference walk).  k_primary is the yardstick of
 (a): the same walk on the same rays, with a 32-byte ray read in place of ray generation.
 
-    python tools/query_bench.py [--launches 50] [--reps 3] [--out FILE] [--sections query,radiance,surface]
+    python tools/query_bench.py [--launches 50] [--reps 3] [--out FILE] [--sections query,radiance,surface,update]
 
 The radiance section (rtg_radiance_rays_device, DeviceScene.radiance_device) runs on the same
 height field and on the path-tracing fixture tests/golden/scenes/pt_cornell.xml at its own size:
@@ -34,6 +34,12 @@ k_primary's 8x8-tile order and in pixel order, with and without the hint,
   (s)  surface_device: 64 B per ray out        (t)  trace_device with normals: 32 B per ray out
 
 on the same rays in the same session; the ratio (s) / (t) is the figure to read.
+
+The update section (rtg_scene_update, rtg_scene_clone; DeviceScene.update / clone) runs on the same
+height field and on a C4-style instanced scene (scenes.config_c4 at one sample), each with a variant
+of the same geometry (light moved; C4: a rotation and a translation of the instances changed): the
+wall-clock time of create, update, clone and clone + update as the median of --setups calls, and the
+render time of the updated scene against a freshly created one, interleaved.
 """
 import argparse
 import os
@@ -241,8 +247,122 @@ def surface_main(args):
     return lines
 
 
+def update_section(args, name, xml_a, xml_b):
+    """Scene set-up times of one scene and its variant (same geometry): lines of text."""
+    import time
+
+    import torch
+
+    import rtgpu
+
+    hs_a, hs_b = rtgpu.HostScene(xml_a), rtgpu.HostScene(xml_b)
+    cam = hs_a.camera(0)
+    w, h = cam["width"], cam["height"]
+    dev = torch.device("cuda:0")
+    st = torch.cuda.current_stream().cuda_stream
+
+    def timed(fn, n):
+        """Wall-clock ms of n calls, each between two device synchronisations."""
+        out = []
+        for _ in range(n):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            out.append((time.perf_counter() - t0) * 1e3)
+        return out
+
+    live = rtgpu.DeviceScene(hs_a, 0)
+    flip = [hs_b, hs_a]
+
+    def create():
+        rtgpu.DeviceScene(hs_b, 0).close()
+
+    def update():
+        flip.reverse()
+        live.update(flip[0], stream=st)
+
+    def clone():
+        live.clone().close()
+
+    def clone_update():
+        c = live.clone()
+        c.update(hs_b, stream=st)
+        torch.cuda.synchronize()
+        c.close()
+
+    for fn in (create, update, clone, clone_update):
+        timed(fn, 2)
+    ms = {"create (rtg_scene_create + destroy)": timed(create, args.setups),
+          "update (rtg_scene_update, in place)": timed(update, 4 * args.setups),
+          "clone (rtg_scene_clone + destroy)": timed(clone, args.setups),
+          "clone + update + destroy": timed(clone_update, args.setups)}
+    # renders: the scene updated to B against a scene freshly created from B, interleaved
+    if flip[0] is not hs_b:
+        update()
+    fresh = rtgpu.DeviceScene(hs_b, 0)
+    bufs = [torch.empty((h, w, 3), dtype=torch.float32, device=dev) for _ in range(2)]
+    scenes_ = (("render, updated scene", live, bufs[0]), ("render, fresh scene", fresh, bufs[1]))
+    for _, ds, buf in scenes_:
+        for _ in range(args.warmup):
+            ds.render_device(buf.data_ptr(), 0, stream=st)
+    torch.cuda.synchronize()
+    assert torch.equal(bufs[0].view(torch.int32), bufs[1].view(torch.int32)), "updated and fresh renders differ"
+    rs = {label: [] for label, _, _ in scenes_}
+    for _ in range(args.reps):
+        for label, ds, buf in scenes_:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(args.launches):
+                ds.render_device(buf.data_ptr(), 0, stream=st)
+            e1.record()
+            e1.synchronize()
+            rs[label].append(e0.elapsed_time(e1) / args.launches)
+    c = hs_a.counts()
+    lines = [f"update: {name} {w}x{h}, {c['objects']} objects, {c['faces']} faces, {c['lights']} lights, device "
+             f"{torch.cuda.get_device_name(0)}; wall clock between device synchronisations, median of {args.setups} calls "
+             f"(update: {4 * args.setups}); renders: {args.launches} launches x {args.reps} interleaved repetitions, "
+             f"the two images equal bit for bit",
+             f"{'case':40s} {'ms (median)':>12s} {'min':>8s} {'max':>8s} {'/ create':>9s}"]
+    base = np.median(ms["create (rtg_scene_create + destroy)"])
+    for label, v in ms.items():
+        lines.append(f"{label:40s} {np.median(v):12.4f} {min(v):8.4f} {max(v):8.4f} {np.median(v) / base:9.4f}")
+    for label, v in rs.items():
+        lines.append(f"{label:40s} {np.median(v):12.4f} {min(v):8.4f} {max(v):8.4f}")
+    return lines
+
+
+def update_main(args):
+    import scenes
+
+    tmp = tempfile.mkdtemp(prefix="query_bench_")
+    os.chdir(tmp)
+
+    def variant(xml, subs):
+        text = open(xml).read()
+        for pat, rep in subs:
+            text, k = re.subn(pat, rep, text, count=1)
+            assert k == 1, pat
+        out = xml[:-4] + "_b.xml"
+        with open(out, "w") as f:
+            f.write(text)
+        return out
+
+    light = r"(<PointLight id=\"1\">\s*<Position>)[^<]*"
+    lines = []
+    xml = scenes.synthetic_heightfield(tmp, K=args.K, width=args.width, height=args.height)
+    lines += update_section(args, f"synthetic_heightfield K={args.K}", xml,
+                            variant(xml, [(light, r"\g<1>1.2 -0.7 1.3"), (r"(<Intensity>)[^<]*", r"\g<1>380 420 400")]))
+    xml = scenes.config_c4(tmp, width=args.width, height=args.height, spp=1)
+    lines += update_section(args, "c4_forest (100 instances of a 10k-triangle tree), 1 spp", xml,
+                            variant(xml, [(light, r"\g<1>4 28 14"), (r"(<Rotation id=\"2\">)[^<]*", r"\g<1>55 0 1 0"),
+                                          (r"(<Translation id=\"9\">)[^<]*", r"\g<1>-9.5 0 3.5")]))
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--setups", type=int, default=9, help="update section: calls per set-up time")
     ap.add_argument("--launches", type=int, default=50)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=5)
@@ -261,6 +381,8 @@ def main():
         text += radiance_main(args)
     if "surface" in sections:
         text += surface_main(args)
+    if "update" in sections:
+        text += update_main(args)
     text = "\n".join(text)
     print(text)
     if out:
