@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <algorithm>
 #include <cstring>
+#include <initializer_list>
 #include <memory>
 #include <string>
 #include <vector>
@@ -166,7 +167,7 @@ struct rtg_scene {
     // scratch of the host-buffer ray queries (rtg_trace_rays, rtg_camera_rays, rtg_radiance_rays,
     // rtg_surface_rays): rays, hits, normals, radiance output, pixel ids, surface output; grown on
     // demand, never touched by the device-buffer entry points
-    void* q_mem[6] = {};
+    void* q_mem[6] = {};              // by QuerySlot (Q_SLOTS of them)
     size_t q_cap[6] = {};
     // block -> tile tables, one per (tiles_x, tiles_y) met (never re-uploaded: kernels of
     // several streams may be reading them)
@@ -1198,8 +1199,20 @@ int rtg_trace_rays_device(rtg_scene* s, const rtg_ray* d_rays, int64_t n, uint32
     return RTG_OK;
 }
 
-// the host-buffer queries' scratch buffer `k` (rtg_scene::q_mem) of at least `bytes`
-static int query_scratch(rtg_scene* s, int k, size_t bytes) {
+// The host-buffer queries' scratch (rtg_scene::q_mem): one slot per kind of buffer
+enum QuerySlot { Q_RAYS, Q_HITS, Q_NORMALS, Q_RADIANCE, Q_PIXEL_IDS, Q_SURFACE, Q_SLOTS };
+static_assert(sizeof(rtg_scene::q_mem) == Q_SLOTS * sizeof(void*), "one scratch buffer per slot");
+// One staged buffer of a call: copied in from `in` before the launch, out to `out` after it
+// (either may be null); bytes == 0: the call does without it
+struct Staged {
+    QuerySlot slot;
+    size_t bytes;
+    const void* in;
+    void* out;
+};
+
+// slot `k` of at least `bytes`
+static int query_scratch(rtg_scene* s, QuerySlot k, size_t bytes) {
     if (s->q_cap[k] >= bytes) return RTG_OK;
     HIP_TRY(hipStreamSynchronize(s->stream));
     if (s->q_mem[k]) { (void)hipFree(s->q_mem[k]); s->q_mem[k] = nullptr; }
@@ -1212,24 +1225,37 @@ static int query_scratch(rtg_scene* s, int k, size_t bytes) {
     return RTG_OK;
 }
 
+// every buffer's capacity first, then the copies in, on the scene's stream
+static int stage(rtg_scene* s, std::initializer_list<Staged> bufs) {
+    for (const Staged& b : bufs)
+        if (b.bytes)
+            if (int rc = query_scratch(s, b.slot, b.bytes)) return rc;
+    for (const Staged& b : bufs)
+        if (b.bytes && b.in) HIP_TRY(hipMemcpyAsync(s->q_mem[b.slot], b.in, b.bytes, hipMemcpyHostToDevice, s->stream));
+    return RTG_OK;
+}
+
+// the copies out, then the stream's end
+static int unstage(rtg_scene* s, std::initializer_list<Staged> bufs) {
+    for (const Staged& b : bufs)
+        if (b.bytes && b.out) HIP_TRY(hipMemcpyAsync(b.out, s->q_mem[b.slot], b.bytes, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return RTG_OK;
+}
+
 int rtg_trace_rays(rtg_scene* s, const rtg_ray* rays, int64_t n, uint32_t flags, rtg_hit* hits, float* normals) {
     int rc = query_args(s, rays, n, flags, hits);
     if (rc || n == 0) return rc;
     if (flags & RTG_QUERY_ANY_HIT) normals = nullptr;
     HIP_TRY(hipSetDevice(s->device));
     const size_t N = (size_t)n;
-    if ((rc = query_scratch(s, 0, N * sizeof(rtg_ray)))) return rc;
-    if ((rc = query_scratch(s, 1, N * sizeof(rtg_hit)))) return rc;
-    if (normals && (rc = query_scratch(s, 2, N * 4 * sizeof(float)))) return rc;
-    rtg_ray* dr = (rtg_ray*)s->q_mem[0];
-    rtg_hit* dh = (rtg_hit*)s->q_mem[1];
-    float4* dn = normals ? (float4*)s->q_mem[2] : nullptr;
-    HIP_TRY(hipMemcpyAsync(dr, rays, N * sizeof(rtg_ray), hipMemcpyHostToDevice, s->stream));
-    HIP_TRY(rtg::launch_query(s->ds, s->feat, dr, (int)n, flags, dh, dn, s->stream));
-    HIP_TRY(hipMemcpyAsync(hits, dh, N * sizeof(rtg_hit), hipMemcpyDeviceToHost, s->stream));
-    if (normals) HIP_TRY(hipMemcpyAsync(normals, dn, N * 4 * sizeof(float), hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    return RTG_OK;
+    const std::initializer_list<Staged> bufs = {{Q_RAYS, N * sizeof(rtg_ray), rays, nullptr},
+                           {Q_HITS, N * sizeof(rtg_hit), nullptr, hits},
+                           {Q_NORMALS, normals ? N * 4 * sizeof(float) : 0, nullptr, normals}};
+    if ((rc = stage(s, bufs))) return rc;
+    HIP_TRY(rtg::launch_query(s->ds, s->feat, (rtg_ray*)s->q_mem[Q_RAYS], (int)n, flags, (rtg_hit*)s->q_mem[Q_HITS],
+                              normals ? (float4*)s->q_mem[Q_NORMALS] : nullptr, s->stream));
+    return unstage(s, bufs);
 }
 
 // the camera record and row range of a camera-ray batch
@@ -1262,13 +1288,11 @@ int rtg_camera_rays(rtg_scene* s, const rtg_render_opts* o, rtg_ray* rays) {
     int rc = camera_rays_args(s, o, rays, C, rb, re);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(s->device));
-    const size_t bytes = (size_t)(re - rb) * C.width * sizeof(rtg_ray);
-    if ((rc = query_scratch(s, 0, bytes))) return rc;
+    const std::initializer_list<Staged> bufs = {{Q_RAYS, (size_t)(re - rb) * C.width * sizeof(rtg_ray), nullptr, rays}};
+    if ((rc = stage(s, bufs))) return rc;
     HIP_TRY(rtg::launch_camera_rays(C, rb, re, o->sample_begin < 0 ? 0 : o->sample_begin, o->seed,
-                                    (rtg_ray*)s->q_mem[0], s->stream));
-    HIP_TRY(hipMemcpyAsync(rays, s->q_mem[0], bytes, hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    return RTG_OK;
+                                    (rtg_ray*)s->q_mem[Q_RAYS], s->stream));
+    return unstage(s, bufs);
 }
 
 // ---- surface queries (rtg_surface.hip)
@@ -1297,15 +1321,12 @@ int rtg_surface_rays(rtg_scene* s, const rtg_ray* rays, int64_t n, uint32_t flag
     if (rc || n == 0) return rc;
     HIP_TRY(hipSetDevice(s->device));
     const size_t N = (size_t)n;
-    if ((rc = query_scratch(s, 0, N * sizeof(rtg_ray)))) return rc;
-    if ((rc = query_scratch(s, 5, N * sizeof(rtg_surface)))) return rc;
-    rtg_ray* dr = (rtg_ray*)s->q_mem[0];
-    rtg_surface* ds = (rtg_surface*)s->q_mem[5];
-    HIP_TRY(hipMemcpyAsync(dr, rays, N * sizeof(rtg_ray), hipMemcpyHostToDevice, s->stream));
-    HIP_TRY(rtg::launch_surface(s->ds, s->shade_sk, s->feat, dr, (int)n, flags, ds, s->stream));
-    HIP_TRY(hipMemcpyAsync(out, ds, N * sizeof(rtg_surface), hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    return RTG_OK;
+    const std::initializer_list<Staged> bufs = {{Q_RAYS, N * sizeof(rtg_ray), rays, nullptr},
+                                                {Q_SURFACE, N * sizeof(rtg_surface), nullptr, out}};
+    if ((rc = stage(s, bufs))) return rc;
+    HIP_TRY(rtg::launch_surface(s->ds, s->shade_sk, s->feat, (rtg_ray*)s->q_mem[Q_RAYS], (int)n, flags,
+                                (rtg_surface*)s->q_mem[Q_SURFACE], s->stream));
+    return unstage(s, bufs);
 }
 
 // ---- radiance queries (rtg_radiance.hip)
@@ -1356,18 +1377,14 @@ int rtg_radiance_rays(rtg_scene* s, const rtg_radiance_opts* o, const rtg_ray* r
     if (rc || n == 0) return rc;
     HIP_TRY(hipSetDevice(s->device));
     const size_t N = (size_t)n;
-    if ((rc = query_scratch(s, 0, N * sizeof(rtg_ray)))) return rc;
-    if ((rc = query_scratch(s, 3, N * 4 * sizeof(float)))) return rc;
-    if (pixel_ids && (rc = query_scratch(s, 4, N * sizeof(int32_t)))) return rc;
-    rtg_ray* dr = (rtg_ray*)s->q_mem[0];
-    float* dc = (float*)s->q_mem[3];
-    int32_t* di = pixel_ids ? (int32_t*)s->q_mem[4] : nullptr;
-    HIP_TRY(hipMemcpyAsync(dr, rays, N * sizeof(rtg_ray), hipMemcpyHostToDevice, s->stream));
-    if (di) HIP_TRY(hipMemcpyAsync(di, pixel_ids, N * sizeof(int32_t), hipMemcpyHostToDevice, s->stream));
-    HIP_TRY(rtg::launch_radiance(s->ds, C, P, s->shade_sk, s->feat, dr, di, dc, s->stream));
-    HIP_TRY(hipMemcpyAsync(rgbt, dc, N * 4 * sizeof(float), hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    return RTG_OK;
+    const std::initializer_list<Staged> bufs = {{Q_RAYS, N * sizeof(rtg_ray), rays, nullptr},
+                           {Q_RADIANCE, N * 4 * sizeof(float), nullptr, rgbt},
+                           {Q_PIXEL_IDS, pixel_ids ? N * sizeof(int32_t) : 0, pixel_ids, nullptr}};
+    if ((rc = stage(s, bufs))) return rc;
+    HIP_TRY(rtg::launch_radiance(s->ds, C, P, s->shade_sk, s->feat, (rtg_ray*)s->q_mem[Q_RAYS],
+                                 pixel_ids ? (int32_t*)s->q_mem[Q_PIXEL_IDS] : nullptr, (float*)s->q_mem[Q_RADIANCE],
+                                 s->stream));
+    return unstage(s, bufs);
 }
 
 int rtg_desc_trace_rays(const rtg_scene_desc* d, const rtg_ray* rays, int64_t n, uint32_t flags, rtg_hit* hits,

@@ -3,11 +3,11 @@
 #include <hip/hip_runtime.h>
 
 #include "rtg_device.hpp"
+#include "rtg_variants.hpp"
 #include "rtgpu.h"
 
 namespace rtg {
 
-int max_supported_depth();
 // large leaves of the camera walk deferred to k_bigleaf (rtg_wave_shade.hip; RTG_DEFER=0: off)
 bool defer_leaves();
 // FNV-1a of a camera's device record (view, image size, samples, renderer flags): the ray-tree and
@@ -20,14 +20,15 @@ inline unsigned long long camera_hash(const DevCamera& C) {
 }
 // fused kernel (rtg_mega.hip): any scene
 // `ev` (nullable): events recorded around every kernel of the last sample pass
-// sk / feat: the scene's shading / traversal features (path-tracing variants, rtg_mega_pt.hip)
+// sk / feat: the scene's shading / traversal features (rtg_variants.hpp mega_variant)
 hipError_t launch_mega(const DevScene& S, const DevCamera& C, const RenderParams& P, float* hdr, unsigned char* ldr,
                        float* accum, DevCounters* counters, bool stats, int sk, int feat, hipStream_t stream,
                        hipEvent_t* ev);
-hipError_t launch_mega_pt(const DevScene& S, const DevCamera& C, const RenderParams& P, float* hdr, unsigned char* ldr,
-                          float* accum, DevCounters* counters, int sk, int feat, hipStream_t stream);
-hipError_t launch_mega_wh(const DevScene& S, const DevCamera& C, const RenderParams& P, float* hdr, unsigned char* ldr,
-                          float* accum, DevCounters* counters, int sk, int feat, hipStream_t stream);
+// its special variants `v` (v.special()): path tracing (rtg_mega_pt.hip), ray trees (rtg_mega_wh.hip)
+hipError_t launch_mega_pt(const MegaVariant& v, const DevScene& S, const DevCamera& C, const RenderParams& P,
+                          float* hdr, unsigned char* ldr, float* accum, DevCounters* counters, hipStream_t stream);
+hipError_t launch_mega_wh(const MegaVariant& v, const DevScene& S, const DevCamera& C, const RenderParams& P,
+                          float* hdr, unsigned char* ldr, float* accum, DevCounters* counters, hipStream_t stream);
 // wavefront pipeline (rtg_wave.hip): scenes without secondary rays / motion blur
 hipError_t launch_wave(const DevScene& S, const DevCamera& C, const RenderParams& P, const WaveBufs& W, float* hdr,
                        unsigned char* ldr, DevCounters* counters, bool stats, int feat, int sk, hipStream_t stream,

@@ -13,53 +13,28 @@
 
 namespace rtg {
 
-// ---------------------------------------------------------------------------
-// Host-side launch helpers
-// ---------------------------------------------------------------------------
-template <int MAXD, bool STATS, bool PT>
-static hipError_t launch_t(const DevScene& S, const DevCamera& C, const RenderParams& P, float* hdr, unsigned char* l,
-                           float* accum, DevCounters* cnt, hipStream_t stream) {
-    hipLaunchKernelGGL((k_render<MAXD, STATS, PT>), dim3(P.num_tiles), dim3(256), 0, stream, S, C, P, hdr, l, accum,
-                       cnt);
-    return hipGetLastError();
-}
-
-int max_supported_depth() { return 32; }
-
+// the general instantiations (the special ones: rtg_mega_pt.hip, rtg_mega_wh.hip)
 template <bool STATS>
-static hipError_t launch_d(const DevScene& S, const DevCamera& C, const RenderParams& P, float* hdr, unsigned char* l,
-                           float* accum, DevCounters* cnt, int sk, int feat, hipStream_t stream) {
-    const int d = S.max_depth;
-    if (C.path_tracing) {
-        if (!STATS) {
-            // the feature-specialised variants (rtg_mega_pt.hip; RTG_MEGA_GENERAL=1: A/B)
-            const hipError_t e = launch_mega_pt(S, C, P, hdr, l, accum, cnt, sk, feat, stream);
-            if (e != hipErrorNotSupported) return e;
-        }
-        // Russian roulette: unbounded GI recursion, cut at 32 ray-tree levels (the frame stack)
-        if (d <= 8 && !C.russian_roulette) return launch_t<8, STATS, true>(S, C, P, hdr, l, accum, cnt, stream);
-        return launch_t<32, STATS, true>(S, C, P, hdr, l, accum, cnt, stream);
-    }
-    if (!STATS) {
-        const hipError_t e = launch_mega_wh(S, C, P, hdr, l, accum, cnt, sk, feat, stream);
-        if (e != hipErrorNotSupported) return e;
-    }
-    if (d <= 0) return launch_t<0, STATS, false>(S, C, P, hdr, l, accum, cnt, stream);
-    if (d <= 8) return launch_t<8, STATS, false>(S, C, P, hdr, l, accum, cnt, stream);
-    return launch_t<32, STATS, false>(S, C, P, hdr, l, accum, cnt, stream);
-}
-
-static hipError_t launch_any(const DevScene& S, const DevCamera& C, const RenderParams& P, float* hdr, unsigned char* l,
-                             float* accum, DevCounters* cnt, bool stats, int sk, int feat, hipStream_t stream) {
-    return stats ? launch_d<true>(S, C, P, hdr, l, accum, cnt, sk, feat, stream)
-                 : launch_d<false>(S, C, P, hdr, l, accum, cnt, sk, feat, stream);
+static hipError_t launch_general(const MegaVariant& v, const DevScene& S, const DevCamera& C, const RenderParams& P,
+                                 float* hdr, unsigned char* l, float* accum, DevCounters* cnt, hipStream_t stream) {
+    return with_general(v, [&](auto D, auto PT) {
+        return launch_render<decltype(D)::value, STATS, decltype(PT)::value>(S, C, P, hdr, l, accum, cnt, stream);
+    });
 }
 
 hipError_t launch_mega(const DevScene& S, const DevCamera& C, const RenderParams& P, float* hdr, unsigned char* l,
                        float* accum, DevCounters* cnt, bool stats, int sk, int feat, hipStream_t stream,
                        hipEvent_t* ev) {
+    const MegaVariant v =
+        mega_variant(S.max_depth, C.path_tracing, C.russian_roulette, sk, feat, stats, mega_general());
     if (ev) (void)hipEventRecord(ev[0], stream);
-    hipError_t e = launch_any(S, C, P, hdr, l, accum, cnt, stats, sk, feat, stream);
+    hipError_t e;
+    if (v.special())
+        e = v.pt ? launch_mega_pt(v, S, C, P, hdr, l, accum, cnt, stream)
+                 : launch_mega_wh(v, S, C, P, hdr, l, accum, cnt, stream);
+    else
+        e = stats ? launch_general<true>(v, S, C, P, hdr, l, accum, cnt, stream)
+                  : launch_general<false>(v, S, C, P, hdr, l, accum, cnt, stream);
     if (ev) (void)hipEventRecord(ev[1], stream);
     return e;
 }

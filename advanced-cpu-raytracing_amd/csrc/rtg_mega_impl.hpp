@@ -1,4 +1,5 @@
-// The fused kernel's device code (rtg_mega.hip, rtg_mega_pt.hip): one thread per pixel walks
+// The fused kernel's device code and its launchers (rtg_mega.hip, rtg_mega_pt.hip,
+// rtg_mega_wh.hip; the ray tree also rtg_radiance.hip's): one thread per pixel walks
 // the pixel's whole ray tree -- PerformShading (raytracer.cpp:65-134) with the recursion of
 // ComputeMirrorReflection / ...Dielectric... / ...Conductor... and, for path-tracing cameras,
 // ComputeGlobalIllumination (raytracer.cpp:135-191) unrolled onto an explicit per-thread stack.
@@ -6,6 +7,7 @@
 
 #include "rtg_common.hpp"
 #include "rtg_node.hpp"
+#include "rtg_variants.hpp"
 
 namespace rtg {
 
@@ -16,7 +18,7 @@ namespace rtg {
 // tracing node's GI ray).  The node steps (shade_node, resume_frame) are rtg_node.hpp's,
 // shared with the wavefront path-tracing pipeline.
 // SK / FEAT: the scene's shading and traversal features (a superset; the path-tracing
-// variants of rtg_mega_pt.hip), everything by default.
+// and ray-tree variants of rtg_variants.hpp mega_variant), everything by default.
 // SRC: where the primary ray comes from.  CameraRay (a render): GenerateRay's ray of the pixel,
 // unbounded, its primary hit seen from the camera's position (also for depth-of-field rays).
 // GivenRay (radiance queries, render_ray below): a caller's ray -- `tmax` bounds the primary ray
@@ -157,6 +159,28 @@ __global__ __launch_bounds__(256, RTG_MEGA_WAVES) void k_render(DevScene S, DevC
         }
     }
     flush_counters<STATS>(cn, counters);
+}
+
+// ---------------------------------------------------------------------------
+// Host-side launch helpers
+// ---------------------------------------------------------------------------
+template <int MAXD, bool STATS, bool PT, int SK = SK_ALL, int FEAT = FEAT_ALL>
+hipError_t launch_render(const DevScene& S, const DevCamera& C, const RenderParams& P, float* hdr, unsigned char* l,
+                         float* accum, DevCounters* cnt, hipStream_t stream) {
+    hipLaunchKernelGGL((k_render<MAXD, STATS, PT, SK, FEAT>), dim3(P.num_tiles), dim3(256), 0, stream, S, C, P, hdr, l,
+                       accum, cnt);
+    return hipGetLastError();
+}
+
+// The feature-specialised sets of one renderer (rtg_mega_pt.hip: PT, rtg_mega_wh.hip: ray trees;
+// heavy to compile, so one translation unit each)
+template <bool PT>
+hipError_t launch_special(const MegaVariant& v, const DevScene& S, const DevCamera& C, const RenderParams& P, float* hdr,
+                          unsigned char* l, float* accum, DevCounters* cnt, hipStream_t stream) {
+    return with_special(v, [&](auto D, auto K, auto F) {
+        return launch_render<decltype(D)::value, false, PT, decltype(K)::value, decltype(F)::value>(S, C, P, hdr, l, accum,
+                                                                                                     cnt, stream);
+    });
 }
 
 }  // namespace rtg

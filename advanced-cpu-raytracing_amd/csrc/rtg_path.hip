@@ -542,31 +542,16 @@ static hipError_t path_run(PathState& T, const PathKernels& K, bool stats, const
     return hipSuccess;
 }
 
-// the fused kernel's frame-stack bound (rtg_mega.hip launch_d)
-static int path_max_depth(const DevScene& S, const DevCamera& C) {
-    return (S.max_depth <= 8 && !C.russian_roulette) ? 8 : 32;
-}
-
 template <bool STATS>
 static TraceFn trace_kernel(int feat) {
-    const bool big = (feat & FEAT_BIGLEAF) != 0;
-    const int base = feat & ~FEAT_BIGLEAF;
-    if (base == 0) return big ? k_path_trace<STATS, FEAT_BIGLEAF> : k_path_trace<STATS, 0>;
-    if (base == FEAT_SPHERE) return big ? k_path_trace<STATS, FEAT_SPHERE | FEAT_BIGLEAF> : k_path_trace<STATS, FEAT_SPHERE>;
-    return big ? k_path_trace<STATS, FEAT_ALL> : k_path_trace<STATS, FEAT_ALL & ~FEAT_BIGLEAF>;
+    return with_trav_feat(feat, [](auto F) -> TraceFn { return k_path_trace<STATS, decltype(F)::value>; });
 }
 
-// step kernel variants: shading features BRDF / BRDF + env, spot, mesh lights / all; traversal
-// features meshes + spheres (small or large leaves) / all.  Counted renders: the general one.
-template <int SK>
-static StepFn step_kernel_sk(int feat) {
-    if (feat & (FEAT_INSTANCE | FEAT_XFORM)) return k_path_step<false, SK, FEAT_ALL>;
-    return (feat & FEAT_BIGLEAF) ? k_path_step<false, SK, FEAT_SPHERE | FEAT_BIGLEAF> : k_path_step<false, SK, FEAT_SPHERE>;
-}
+// the step kernel of uncounted renders (rtg_variants.hpp step_variant); counted ones: the general one
 static StepFn step_kernel(int sk, int feat) {
-    if ((sk & ~SK_BRDF) == 0) return step_kernel_sk<SK_BRDF>(feat);
-    if ((sk & ~(SK_BRDF | SK_XLIGHT)) == 0) return step_kernel_sk<SK_BRDF | SK_XLIGHT>(feat);
-    return step_kernel_sk<SK_ALL>(feat);
+    return with_step_variant(sk, feat, [](auto K, auto F) -> StepFn {
+        return k_path_step<false, decltype(K)::value, decltype(F)::value>;
+    });
 }
 
 hipError_t launch_path(PathState*& T, const DevScene& S, const DevCamera& C, const RenderParams& P, float* hdr,
@@ -583,7 +568,9 @@ hipError_t launch_path(PathState*& T, const DevScene& S, const DevCamera& C, con
         K.trace = trace_kernel<false>(feat);
         K.step = step_kernel(sk, feat);
     }
-    return path_run(*T, K, stats, S, C, P, path_max_depth(S, C), hdr, l, accum, cnt, st, ev);
+    // the frame stacks' depth: the fused kernel's, whose images the passes reproduce
+    const int maxd = mega_variant(S.max_depth, true, C.russian_roulette, sk, feat, stats, mega_general()).maxd;
+    return path_run(*T, K, stats, S, C, P, maxd, hdr, l, accum, cnt, st, ev);
 }
 
 }  // namespace rtg

@@ -79,9 +79,8 @@ static hipError_t launch_query_f(const DevScene& S, const rtg_ray* rays, int n, 
     const float4* R = reinterpret_cast<const float4*>(rays);
     int4* H = reinterpret_cast<int4*>(hits);
     if (flags & RTG_QUERY_ANY_HIT) {
-        // the wide walk where the render's shadow rays take it (rtg_wave.hpp launch_wave_t `fast`,
-        // without the deferral queues)
-        const bool fast = S.anodes != nullptr && (!(FEAT & FEAT_BIGLEAF) || S.ahb_split) && !S.exact_shadow;
+        // the wide walk where the render's shadow rays take it, without the deferral queues
+        const bool fast = any_hit_wide(S, FEAT);
         if (fast) hipLaunchKernelGGL((k_query<true, FEAT, true>), grid, block, 0, st, S, R, n, H, nullptr);
         else hipLaunchKernelGGL((k_query<true, FEAT, false>), grid, block, 0, st, S, R, n, H, nullptr);
         return hipGetLastError();
@@ -100,21 +99,9 @@ static hipError_t launch_query_f(const DevScene& S, const rtg_ray* rays, int n, 
 
 hipError_t launch_query(const DevScene& S, int feat, const rtg_ray* rays, int n, uint32_t flags, rtg_hit* hits,
                         float4* normals, hipStream_t stream) {
-    // the traversal variants of the wavefront pipeline (rtg_wave_shade.hip launch_wave)
-    const bool big = (feat & FEAT_BIGLEAF) != 0;
-    const int base = feat & ~FEAT_BIGLEAF;
-#define RTG_QUERY(F) return launch_query_f<F>(S, rays, n, flags, hits, normals, stream)
-    if (base == 0) {
-        if (big) RTG_QUERY(FEAT_BIGLEAF);
-        RTG_QUERY(0);
-    }
-    if (base == FEAT_SPHERE) {
-        if (big) RTG_QUERY(FEAT_SPHERE | FEAT_BIGLEAF);
-        RTG_QUERY(FEAT_SPHERE);
-    }
-    if (big) RTG_QUERY(FEAT_ALL);
-    RTG_QUERY(FEAT_ALL & ~FEAT_BIGLEAF);
-#undef RTG_QUERY
+    return with_trav_feat(feat, [&](auto F) {
+        return launch_query_f<decltype(F)::value>(S, rays, n, flags, hits, normals, stream);
+    });
 }
 
 hipError_t launch_camera_rays(const DevCamera& C, int row_begin, int row_end, int sample, unsigned long long seed,

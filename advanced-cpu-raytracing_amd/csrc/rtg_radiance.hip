@@ -5,10 +5,9 @@
 //               root_key(seed, p, s), the key k_render gives that pixel and sample, so the camera's
 //               own rays (rtg_camera_rays) give the render's image bit for bit.
 //
-// The instantiations and their dispatch are k_render's (rtg_mega.hip launch_d, rtg_mega_pt.hip,
-// rtg_mega_wh.hip): PT from the camera, MAXD from the scene's depth and the Russian-roulette rule,
-// the feature-specialised (SK, FEAT) sets under the same conditions.
-#include <cstdlib>
+// The instantiations and their dispatch are k_render's: the uncounted render's variant
+// (rtg_variants.hpp mega_variant) -- PT from the camera, MAXD from the scene's depth and the
+// Russian-roulette rule, the feature-specialised (SK, FEAT) sets under the same conditions.
 
 // the fused kernels keep trav_ray's ray unlaundered (rtg_common.hpp: laundering it costs C2
 // 6 %, profiles/r05ag_sphere_launder_ab.txt)
@@ -67,43 +66,25 @@ static hipError_t launch_t(const DevScene& S, const DevCamera& C, const Radiance
     return hipGetLastError();
 }
 
-// ---- the feature-specialised variants: rtg_mega_pt.hip's / rtg_mega_wh.hip's sets and conditions
-template <int MAXD, bool PT, int SK>
-static hipError_t launch_feat(const DevScene& S, const DevCamera& C, const RadianceParams& P, const rtg_ray* rays,
-                              const int* ids, float* rgbt, int feat, hipStream_t stream) {
-    if (feat & FEAT_BIGLEAF) return launch_t<MAXD, PT, SK, FEAT_SPHERE | FEAT_BIGLEAF>(S, C, P, rays, ids, rgbt, stream);
-    return launch_t<MAXD, PT, SK, FEAT_SPHERE>(S, C, P, rays, ids, rgbt, stream);
-}
-
-template <int MAXD, bool PT>
-static hipError_t launch_sk(const DevScene& S, const DevCamera& C, const RadianceParams& P, const rtg_ray* rays,
-                            const int* ids, float* rgbt, int sk, int feat, hipStream_t stream) {
-    if ((sk & ~SK_BRDF) == 0) return launch_feat<MAXD, PT, SK_BRDF>(S, C, P, rays, ids, rgbt, feat, stream);
-    return launch_feat<MAXD, PT, SK_BRDF | SK_XLIGHT>(S, C, P, rays, ids, rgbt, feat, stream);
+template <bool PT>
+static hipError_t launch_radiance_special(const MegaVariant& v, const DevScene& S, const DevCamera& C,
+                                          const RadianceParams& P, const rtg_ray* rays, const int* ids, float* rgbt,
+                                          hipStream_t stream) {
+    return with_special(v, [&](auto D, auto K, auto F) {
+        return launch_t<decltype(D)::value, PT, decltype(K)::value, decltype(F)::value>(S, C, P, rays, ids, rgbt, stream);
+    });
 }
 
 hipError_t launch_radiance(const DevScene& S, const DevCamera& C, const RadianceParams& P, int sk, int feat,
                            const rtg_ray* rays, const int* ids, float* rgbt, hipStream_t stream) {
-    const int d = S.max_depth;
-    // RTG_MEGA_GENERAL=1: the general instantiations always (A/B, as for the renders)
-    const bool special = !(sk & SK_TEX) && !(feat & (FEAT_INSTANCE | FEAT_XFORM)) && !std::getenv("RTG_MEGA_GENERAL");
-    if (C.path_tracing) {
-        // Russian roulette: unbounded GI recursion, cut at 32 ray-tree levels (the frame stack)
-        const bool d8 = d <= 8 && !C.russian_roulette;
-        if (special) {
-            if (d8) return launch_sk<8, true>(S, C, P, rays, ids, rgbt, sk, feat, stream);
-            return launch_sk<32, true>(S, C, P, rays, ids, rgbt, sk, feat, stream);
-        }
-        if (d8) return launch_t<8, true>(S, C, P, rays, ids, rgbt, stream);
-        return launch_t<32, true>(S, C, P, rays, ids, rgbt, stream);
-    }
-    if (special && d > 0) {
-        if (d <= 8) return launch_sk<8, false>(S, C, P, rays, ids, rgbt, sk, feat, stream);
-        return launch_sk<32, false>(S, C, P, rays, ids, rgbt, sk, feat, stream);
-    }
-    if (d <= 0) return launch_t<0, false>(S, C, P, rays, ids, rgbt, stream);
-    if (d <= 8) return launch_t<8, false>(S, C, P, rays, ids, rgbt, stream);
-    return launch_t<32, false>(S, C, P, rays, ids, rgbt, stream);
+    // the render's variant, uncounted
+    const MegaVariant v = mega_variant(S.max_depth, C.path_tracing, C.russian_roulette, sk, feat, false, mega_general());
+    if (v.special())
+        return v.pt ? launch_radiance_special<true>(v, S, C, P, rays, ids, rgbt, stream)
+                    : launch_radiance_special<false>(v, S, C, P, rays, ids, rgbt, stream);
+    return with_general(v, [&](auto D, auto PT) {
+        return launch_t<decltype(D)::value, decltype(PT)::value>(S, C, P, rays, ids, rgbt, stream);
+    });
 }
 
 }  // namespace rtg

@@ -87,23 +87,11 @@ static hipError_t launch_surface_f(const DevScene& S, const rtg_ray* rays, int n
 
 hipError_t launch_surface(const DevScene& S, int sk, int feat, const rtg_ray* rays, int n, uint32_t flags, rtg_surface* out,
                           hipStream_t stream) {
-    // the FEAT sets of launch_query
-    const bool big = (feat & FEAT_BIGLEAF) != 0;
-    const int base = feat & ~FEAT_BIGLEAF;
-#define RTG_SURFACE(F) \
-    return (sk & SK_TEX) ? launch_surface_f<F, true>(S, rays, n, flags, out, stream) \
-                         : launch_surface_f<F, false>(S, rays, n, flags, out, stream)
-    if (base == 0) {
-        if (big) RTG_SURFACE(FEAT_BIGLEAF);
-        RTG_SURFACE(0);
-    }
-    if (base == FEAT_SPHERE) {
-        if (big) RTG_SURFACE(FEAT_SPHERE | FEAT_BIGLEAF);
-        RTG_SURFACE(FEAT_SPHERE);
-    }
-    if (big) RTG_SURFACE(FEAT_ALL);
-    RTG_SURFACE(FEAT_ALL & ~FEAT_BIGLEAF);
-#undef RTG_SURFACE
+    return with_trav_feat(feat, [&](auto F) {
+        constexpr int FEAT = decltype(F)::value;
+        return (sk & SK_TEX) ? launch_surface_f<FEAT, true>(S, rays, n, flags, out, stream)
+                             : launch_surface_f<FEAT, false>(S, rays, n, flags, out, stream);
+    });
 }
 
 }  // namespace rtg

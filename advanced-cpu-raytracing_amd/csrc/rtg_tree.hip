@@ -600,7 +600,7 @@ static void level_launches(TreeState& T, const DevScene& S, const DevCamera& C, 
                            hipStream_t st) {
     if (level == 0) hipLaunchKernelGGL(k_tree_gen, dim3(blocks), dim3(256), 0, st, C, P, s, L);
     hipLaunchKernelGGL((k_tree_trace<STATS, FEAT>), dim3(blocks), dim3(256), 0, st, S, L, level, cnt);
-    if ((T.sk & ~SK_TEX) == 0)
+    if (tree_shade_sk(T.sk) == SK_TEX)
         hipLaunchKernelGGL((k_tree_shade<STATS, SK_TEX>), dim3(blocks), dim3(256), 0, st, S, C, L, level, P, T.G, cnt);
     else
         hipLaunchKernelGGL((k_tree_shade<STATS, SK_ALL>), dim3(blocks), dim3(256), 0, st, S, C, L, level, P, T.G, cnt);
@@ -876,22 +876,11 @@ hipError_t launch_tree(TreeState*& T, const DevScene& S, const DevCamera& C, con
                        hipStream_t st, hipEvent_t* ev) {
     if (!T) T = new TreeState();
     T->sk = sk;
-    const bool big = (feat & FEAT_BIGLEAF) != 0;
-    const int base = feat & ~FEAT_BIGLEAF;
-#define RTG_TREE(F)                                                                     \
-    return stats ? tree_run<true, F>(*T, S, C, P, hdr, l, accum, cnt, st, ev)           \
-                 : tree_run<false, F>(*T, S, C, P, hdr, l, accum, cnt, st, ev)
-    if (base == 0) {
-        if (big) RTG_TREE(FEAT_BIGLEAF);
-        RTG_TREE(0);
-    }
-    if (base == FEAT_SPHERE) {
-        if (big) RTG_TREE(FEAT_SPHERE | FEAT_BIGLEAF);
-        RTG_TREE(FEAT_SPHERE);
-    }
-    if (big) RTG_TREE(FEAT_ALL);
-    RTG_TREE(FEAT_ALL & ~FEAT_BIGLEAF);
-#undef RTG_TREE
+    return with_trav_feat(feat, [&](auto F) {
+        constexpr int FEAT = decltype(F)::value;
+        return stats ? tree_run<true, FEAT>(*T, S, C, P, hdr, l, accum, cnt, st, ev)
+                     : tree_run<false, FEAT>(*T, S, C, P, hdr, l, accum, cnt, st, ev);
+    });
 }
 
 }  // namespace rtg

@@ -820,7 +820,7 @@ hipError_t launch_wave_t(const DevScene& S, const DevCamera& C, const RenderPara
     // (k_bigleaf_any; RTG_DEFER_ANY=0: the cooperative reference walk)
     const bool defer_any = !STATS && (FEAT & FEAT_BIGLEAF) && W.dq_e && W.shadow_state &&
                            S.anodes && !S.ahb_split && !S.exact_shadow && defer_any_leaves();
-    const bool fast = S.anodes != nullptr && (!(FEAT & FEAT_BIGLEAF) || S.ahb_split || defer_any) && !S.exact_shadow;
+    const bool fast = any_hit_wide(S, FEAT, defer_any);
     // shading fused with the shadow ray: plain shading, the fast any-hit walk
     const bool fused = scene_sk == 0 && fast && !(FEAT & FEAT_BIGLEAF) && nshadow > 0;
     *layout = fused ? (frame_kernel() && !(FEAT == 0 && S.ordered) ? LAYOUT_WAVE_FRAME : LAYOUT_WAVE_FUSED)
@@ -944,17 +944,15 @@ hipError_t launch_wave_f(const DevScene& S, const DevCamera& C, const RenderPara
     return stats ? launch_wave_t<true, FEAT>(S, C, P, W, hdr, l, cnt, sk, st, ev, layout)
                  : launch_wave_t<false, FEAT>(S, C, P, W, hdr, l, cnt, sk, st, ev, layout);
 }
-// traversal variants, split over two translation units (compile time)
-#define RTG_WAVE_DECL(F)                                                                                          \
-    extern template hipError_t launch_wave_f<F>(const DevScene&, const DevCamera&, const RenderParams&,             \
-                                                const WaveBufs&, float*, unsigned char*, DevCounters*, bool, int, \
-                                                hipStream_t, hipEvent_t*, int*);
-RTG_WAVE_DECL(0)
-RTG_WAVE_DECL(FEAT_SPHERE)
-RTG_WAVE_DECL(FEAT_BIGLEAF)
-RTG_WAVE_DECL(FEAT_SPHERE | FEAT_BIGLEAF)
-RTG_WAVE_DECL(FEAT_ALL)
-RTG_WAVE_DECL(FEAT_ALL & ~FEAT_BIGLEAF)
+// traversal variants (rtg_variants.hpp), split over two translation units (compile time):
+// rtg_wave_a.hip instantiates RTG_TRAV_FEATS_SMALL, rtg_wave_b.hip RTG_TRAV_FEATS_BIG
+#define RTG_WAVE_INST(F)                                                                                     \
+    template hipError_t launch_wave_f<(F)>(const DevScene&, const DevCamera&, const RenderParams&,            \
+                                           const WaveBufs&, float*, unsigned char*, DevCounters*, bool, int, \
+                                           hipStream_t, hipEvent_t*, int*);
+#define RTG_WAVE_DECL(F) extern RTG_WAVE_INST(F)
+RTG_TRAV_FEATS_SMALL(RTG_WAVE_DECL)
+RTG_TRAV_FEATS_BIG(RTG_WAVE_DECL)
 #undef RTG_WAVE_DECL
 
 }  // namespace rtg

@@ -117,22 +117,9 @@ void wave_accum(const DevCamera& C, const RenderParams& P, int sample, const Wav
 hipError_t launch_wave(const DevScene& S, const DevCamera& C, const RenderParams& P, const WaveBufs& W, float* hdr,
                        unsigned char* l, DevCounters* cnt, bool stats, int feat, int sk, hipStream_t stream,
                        hipEvent_t* ev, int* layout) {
-    // traversal variants: meshes only (identity transforms) / + spheres / everything,
-    // each with the sequential or the cooperative (large-leaf) BVH walk
-    const bool big = (feat & FEAT_BIGLEAF) != 0;
-    const int base = feat & ~FEAT_BIGLEAF;
-#define RTG_WAVE(F) return launch_wave_f<F>(S, C, P, W, hdr, l, cnt, stats, sk, stream, ev, layout)
-    if (base == 0) {
-        if (big) RTG_WAVE(FEAT_BIGLEAF);
-        RTG_WAVE(0);
-    }
-    if (base == FEAT_SPHERE) {
-        if (big) RTG_WAVE(FEAT_SPHERE | FEAT_BIGLEAF);
-        RTG_WAVE(FEAT_SPHERE);
-    }
-    if (big) RTG_WAVE(FEAT_ALL);
-    RTG_WAVE(FEAT_ALL & ~FEAT_BIGLEAF);
-#undef RTG_WAVE
+    return with_trav_feat(feat, [&](auto F) {
+        return launch_wave_f<decltype(F)::value>(S, C, P, W, hdr, l, cnt, stats, sk, stream, ev, layout);
+    });
 }
 
 }  // namespace rtg

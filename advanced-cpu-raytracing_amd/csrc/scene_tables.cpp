@@ -7,7 +7,7 @@
 #include <cstdio>
 #include <cstring>
 
-#include "rtg_kernels.hpp"   // max_supported_depth
+#include "rtg_variants.hpp"   // max_supported_depth
 
 namespace rtg {
 namespace {

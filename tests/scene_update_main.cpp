@@ -22,9 +22,6 @@
 #include "host_scene.hpp"
 #include "scene_tables.hpp"
 
-// The kernels' ray-tree depth bound (rtg_mega.hip, not linked here); validate_desc reads it.
-namespace rtg { int max_supported_depth() { return 32; } }
-
 namespace {
 
 std::string g_where;
