@@ -17,9 +17,11 @@
 #include "host_query.hpp"
 #include "host_scene.hpp"
 #include "rtg_device.hpp"
+#include "rtg_devmem.hpp"
 #include "rtg_kernels.hpp"
 #include "rtgpu.h"
 #include "scene_tables.hpp"
+#include "work_layout.hpp"
 
 namespace {
 
@@ -41,61 +43,19 @@ int set_err(int code, const char* fmt, ...) {
         if (e_ != hipSuccess) return set_err(RTG_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 
-template <typename T>
-struct DevBuf {
-    T* p = nullptr;
-    size_t n = 0;      // entries in use
-    size_t cap = 0;    // entries allocated (>= n: update() keeps an allocation that is large enough)
-    DevBuf() = default;
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    // what the kernels are handed: null for an empty table, as after upload()
-    T* ptr() const { return n ? p : nullptr; }
-    hipError_t alloc(size_t count) {
-        if (p) { (void)hipFree(p); p = nullptr; }
-        n = cap = count;
-        return count ? hipMalloc(&p, count * sizeof(T)) : hipSuccess;
-    }
-    hipError_t upload(const std::vector<T>& v) {
-        if (p) { (void)hipFree(p); p = nullptr; }   // hipFree waits for the device
-        n = cap = v.size();
-        if (n == 0) return hipSuccess;
-        hipError_t e = hipMalloc(&p, n * sizeof(T));
-        if (e != hipSuccess) { n = cap = 0; return e; }
-        return hipMemcpy(p, v.data(), n * sizeof(T), hipMemcpyHostToDevice);
-    }
-    // In place on `st` where `v` fits the allocation: work enqueued on `st` before sees the old
-    // entries, work after it the new ones; `v` must outlive the copy.  A table that outgrows its
-    // capacity is reallocated: hipFree waits for the device (every stream's work), and p changes.
-    hipError_t update(const std::vector<T>& v, hipStream_t st) {
-        if (v.size() > cap) {
-            if (p) { (void)hipFree(p); p = nullptr; }
-            n = cap = 0;
-            hipError_t e = hipMalloc(&p, v.size() * sizeof(T));
-            if (e != hipSuccess) return e;
-            cap = v.size();
-        }
-        n = v.size();
-        return n ? hipMemcpyAsync(p, v.data(), n * sizeof(T), hipMemcpyHostToDevice, st) : hipSuccess;
-    }
-};
-
 }  // namespace
 
-// Wavefront work buffers of one render context (rtg_scene::work).
+using rtg::DevBuf;
+
+// Wavefront work buffers of a scene (rtg_scene::work), each one allocation carved by
+// work_layout.hpp for the shape beside it.
 struct WaveWork {
-    size_t pixels = 0, tiles = 0;
-    int slots = 0;
-    bool col = false;                 // with the multi-sample colour buffer
-    int pay = 0;                      // one-layout payload float4s per queue entry
-    void* mem = nullptr;
-    void* dq = nullptr;               // deferred-leaf queue + per-pixel hit keys (ensure_defer)
-    size_t dq_nq = 0;                 // its shadow-state entries
-    size_t dq_pixels = 0;             // the pixel count its hit-key array (and so its layout) was sized for
+    DevBuf<char> mem;                 // ensure_wave
+    rtg::WaveShape shape;
+    DevBuf<char> dq;                  // deferred-leaf queue + per-pixel hit keys (ensure_defer)
+    rtg::DeferShape dq_shape;         // (its pixel count decides its layout)
     rtg::WaveBufs W{};
 };
-constexpr int kWorkCtx = 1;
 struct TileMap {
     int tx, ty;
     DevBuf<int> map;
@@ -119,6 +79,9 @@ struct SceneGeom {
     DevBuf<int> perm;
     DevBuf<float> grad;
 };
+
+// The host-buffer queries' scratch (rtg_scene::q): one slot per kind of buffer
+enum QuerySlot { Q_RAYS, Q_HITS, Q_NORMALS, Q_RADIANCE, Q_PIXEL_IDS, Q_SURFACE, Q_SLOTS };
 
 struct rtg_scene {
     int device = 0;
@@ -159,16 +122,14 @@ struct rtg_scene {
     int num_slots = 0;                // lights per pixel (wavefront light slots)
     int shade_sk = rtg::SK_ALL;       // shading features (k_shade variant, rtg_common.hpp SK_*)
     // wavefront buffers, grown on demand
-    WaveWork work[kWorkCtx];
-    // scratch for the host-buffer entry point
-    float* d_hdr = nullptr;
-    unsigned char* d_ldr = nullptr;
-    size_t d_pixels = 0;
+    WaveWork work;
+    // scratch for the host-buffer entry point (both of the same pixel count)
+    DevBuf<float> d_hdr;
+    DevBuf<unsigned char> d_ldr;
     // scratch of the host-buffer ray queries (rtg_trace_rays, rtg_camera_rays, rtg_radiance_rays,
     // rtg_surface_rays): rays, hits, normals, radiance output, pixel ids, surface output; grown on
     // demand, never touched by the device-buffer entry points
-    void* q_mem[6] = {};              // by QuerySlot (Q_SLOTS of them)
-    size_t q_cap[6] = {};
+    DevBuf<char> q[Q_SLOTS];          // by QuerySlot, in bytes
     // block -> tile tables, one per (tiles_x, tiles_y) met (never re-uploaded: kernels of
     // several streams may be reading them)
     std::vector<std::unique_ptr<TileMap>> tile_maps;
@@ -200,14 +161,7 @@ struct rtg_scene {
         if (stream) (void)hipStreamDestroy(stream);
         for (auto& e : ev)
             if (e) (void)hipEventDestroy(e);
-        if (d_hdr) (void)hipFree(d_hdr);
-        if (d_ldr) (void)hipFree(d_ldr);
-        for (void* q : q_mem)
-            if (q) (void)hipFree(q);
-        for (auto& w : work) {
-            if (w.mem) (void)hipFree(w.mem);
-            if (w.dq) (void)hipFree(w.dq);
-        }
+        // (the members' device memory is freed after this body, on the device set above)
     }
 };
 
@@ -304,13 +258,11 @@ static int build_bvh_on_device(SceneGeom* sc, const rtg_scene_desc* d, bool reco
     if (anyUV) HIP_TRY(sc->face_uv.alloc(3 * F));
     if (anyMapped) HIP_TRY(sc->face_v12.alloc(2 * F));
     HIP_TRY(hipMemset(sc->nodes.p, 0, sc->nodes.n * sizeof(float4)));
-    rtg_face* dfaces = nullptr;
-    int* dperm = nullptr;
-    HIP_TRY(hipMalloc(&dfaces, F * sizeof(rtg_face)));
-    struct Free { void* p; ~Free() { if (p) (void)hipFree(p); } } freeFaces{dfaces};
-    HIP_TRY(hipMemcpy(dfaces, d->faces, F * sizeof(rtg_face), hipMemcpyHostToDevice));
-    HIP_TRY(hipMalloc(&dperm, F * sizeof(int)));
-    Free freePerm{dperm};
+    DevBuf<rtg_face> faces;
+    DevBuf<int> perm;
+    HIP_TRY(faces.alloc(F));
+    HIP_TRY(hipMemcpy(faces.p, d->faces, F * sizeof(rtg_face), hipMemcpyHostToDevice));
+    HIP_TRY(perm.alloc(F));
     hipStream_t st = nullptr;
     int nodeBase = 0;
     rb.mesh_begin.resize(d->num_meshes);
@@ -326,10 +278,10 @@ static int build_bvh_on_device(SceneGeom* sc, const rtg_scene_desc* d, bool reco
         if (!owner) return set_err(RTG_ERR_INVALID, "mesh %d: no Mesh object carries its bbox", m);
         int count = 0;
         bool bl = false;
-        HIP_TRY(rtg::build_mesh_bvh(dfaces + M.face_offset, M.face_count, owner->bbox_min, owner->bbox_max,
+        HIP_TRY(rtg::build_mesh_bvh(faces.p + M.face_offset, M.face_count, owner->bbox_min, owner->bbox_max,
                                     M.face_offset, nodeBase, sc->nodes.p, sc->node_ext.p, sc->tris.p, sc->face_n.p,
                                     anyUV ? sc->face_uv.p : nullptr, anyMapped ? sc->face_v12.p : nullptr,
-                                    dperm + M.face_offset, &count, &bl, st));
+                                    perm.p + M.face_offset, &count, &bl, st));
         rb.mesh_begin[m] = nodeBase;
         rb.mesh_end[m] = nodeBase + count;
         nodeBase += count;
@@ -337,7 +289,7 @@ static int build_bvh_on_device(SceneGeom* sc, const rtg_scene_desc* d, bool reco
     }
     rb.node_count = nodeBase + 1;                       // + the zeroed pad node
     rb.perm.resize(F);
-    HIP_TRY(hipMemcpy(rb.perm.data(), dperm, F * sizeof(int), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(rb.perm.data(), perm.p, F * sizeof(int), hipMemcpyDeviceToHost));
     for (int m = 0; m < d->num_meshes; ++m)
         for (int k = 0; k < d->meshes[m].face_count; ++k) rb.perm[d->meshes[m].face_offset + k] += d->meshes[m].face_offset;
     if (records) {
@@ -806,71 +758,50 @@ static int one_payload(const rtg_scene* s) {
 // payload float4s per queue entry (one_payload); `col`: with the colour buffer of multi-sample
 // passes (one float4 per entry).
 static int ensure_wave(WaveWork& ww, size_t pixels, int slots, size_t tiles, int pay, bool col = false) {
-    if (ww.mem && ww.pixels >= pixels && ww.slots >= slots && ww.tiles >= tiles && ww.pay >= pay && (ww.col || !col))
-        return RTG_OK;
-    if (ww.dq) { (void)hipFree(ww.dq); ww.dq = nullptr; }
-    if (ww.mem) { (void)hipFree(ww.mem); ww.mem = nullptr; }
-    pixels = std::max(pixels, ww.pixels);
-    tiles = std::max(tiles, ww.tiles);
-    col = col || ww.col;
-    pay = std::max(pay, ww.pay);
-    const size_t ns = pixels * (size_t)std::max(slots, 1);
-    const size_t nq = tiles * 256 * (size_t)std::max(slots, 1);
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    size_t off[13], total = 0;
-    const size_t sz[13] = {pixels * 4, pixels * 4, pixels * 4, pixels * 16, ns * 16, ns, nq * 16, nq * 16, nq * 4,
-                           tiles * 4, pixels * 16, (size_t)tiles * 256 * 16 * pay, col ? pixels * 16 : 0};
-    for (int k = 0; k < 13; ++k) { off[k] = total; total += al(sz[k]); }
-    HIP_TRY(hipMalloc(&ww.mem, total));
-    char* b = (char*)ww.mem;
+    const rtg::WaveShape want{pixels, tiles, slots, pay, col};
+    if (ww.mem.p && ww.shape.covers(want)) return RTG_OK;
+    ww.dq.release();
+    ww.dq_shape = {};
+    ww.mem.release();
+    const rtg::WaveShape sh = ww.shape.merged(want);
+    const rtg::WaveLayout L = rtg::wave_layout(sh);
+    HIP_TRY(ww.mem.reserve(L.total));
+    auto at = [&](rtg::WavePiece k) { return (void*)(ww.mem.p + L.off[k]); };
     rtg::WaveBufs& W = ww.W;
-    W.hit_t = (float*)(b + off[0]); W.hit_obj = (int*)(b + off[1]); W.hit_face = (int*)(b + off[2]);
-    W.base = (float4*)(b + off[3]); W.term = (float4*)(b + off[4]); W.occ = (unsigned char*)(b + off[5]);
-    W.q_o = (float4*)(b + off[6]); W.q_d = (float4*)(b + off[7]); W.q_slot = (int*)(b + off[8]);
-    W.q_count = (int*)(b + off[9]); W.accum = (float4*)(b + off[10]);
-    W.q_pay = pay ? (float4*)(b + off[11]) : nullptr;
-    W.pay3 = pay == 3;
-    ww.pay = pay;
-    W.col = col ? (float4*)(b + off[12]) : nullptr;
-    ww.col = col;
-    ww.pixels = pixels;
-    ww.slots = slots;
-    ww.tiles = tiles;
+    W.hit_t = (float*)at(rtg::WP_HIT_T); W.hit_obj = (int*)at(rtg::WP_HIT_OBJ); W.hit_face = (int*)at(rtg::WP_HIT_FACE);
+    W.base = (float4*)at(rtg::WP_BASE); W.term = (float4*)at(rtg::WP_TERM); W.occ = (unsigned char*)at(rtg::WP_OCC);
+    W.q_o = (float4*)at(rtg::WP_Q_O); W.q_d = (float4*)at(rtg::WP_Q_D); W.q_slot = (int*)at(rtg::WP_Q_SLOT);
+    W.q_count = (int*)at(rtg::WP_Q_COUNT); W.accum = (float4*)at(rtg::WP_ACCUM);
+    W.q_pay = sh.pay ? (float4*)at(rtg::WP_Q_PAY) : nullptr;
+    W.pay3 = sh.pay == 3;
+    W.col = sh.col ? (float4*)at(rtg::WP_COL) : nullptr;
+    ww.shape = sh;
     W.dq_e = nullptr;
     W.dq_count = nullptr;
     W.hit_key = nullptr;
     W.shadow_state = nullptr;
     W.dq_cap = 0;
-    ww.dq_nq = 0;
-    ww.dq_pixels = 0;
     return RTG_OK;
 }
 
-// The deferred-leaf queue of a large-leaf scene's camera walk (WaveBufs dq_*, hit_key): two
-// entries per pixel of capacity (an entry that does not fit is tested in the walk).
-// Layout [256 B counts | pixels x 8 B keys | cap x 48 B entries | nq x 4 B states]: the entry
-// and state offsets depend on the pixel count, so a buffer laid out for fewer pixels is never
-// reused (the 1 024-entry floor on cap alone would let keys overrun the entries).
-static int ensure_defer(WaveWork& ww, size_t pixels, size_t nq) {
-    if (ww.dq && ww.dq_pixels >= pixels && ww.W.dq_cap >= (int)std::max<size_t>(2 * pixels, 1024) && ww.dq_nq >= nq)
-        return RTG_OK;
-    if (ww.dq) { (void)hipFree(ww.dq); ww.dq = nullptr; }
-    nq = std::max(nq, ww.dq_nq);
-    pixels = std::max(pixels, ww.dq_pixels);
-    const size_t cap = std::max<size_t>(2 * pixels, 1024);
-    const size_t bytes = 256 + pixels * 8 + cap * 48 + nq * 4;
-    HIP_TRY(hipMalloc(&ww.dq, bytes));
+// The deferred-leaf queue of a large-leaf scene's camera walk (work_layout.hpp defer_layout),
+// for a pass of `pixels` entries and `nq` shadow-queue entries on stream `st`.
+static int ensure_defer(WaveWork& ww, size_t pixels, size_t nq, hipStream_t st) {
+    const rtg::DeferShape want{pixels, nq};
+    if (ww.dq.p && ww.dq_shape.covers(want)) return RTG_OK;
+    const rtg::DeferShape sh = ww.dq_shape.merged(want);
+    const rtg::DeferLayout L = rtg::defer_layout(sh.pixels, sh.nq);
+    HIP_TRY(ww.dq.reserve(L.total));
     // the counters start at zero; the kernels after their last readers zero them for the next
     // pass (k_shade: camera entries / unsettled pixels, k_shadow_fin*: shadow entries)
-    HIP_TRY(hipMemset(ww.dq, 0, 256));
-    char* b = (char*)ww.dq;
-    ww.W.dq_count = (int*)b;
-    ww.W.hit_key = (unsigned long long*)(b + 256);
-    ww.W.dq_e = (float4*)(b + 256 + pixels * 8);
-    ww.W.shadow_state = (int*)(b + 256 + pixels * 8 + cap * 48);
-    ww.W.dq_cap = (int)cap;
-    ww.dq_nq = nq;
-    ww.dq_pixels = pixels;
+    HIP_TRY(hipMemsetAsync(ww.dq.p, 0, 256, st));
+    char* b = ww.dq.p;
+    ww.W.dq_count = (int*)(b + L.counts);
+    ww.W.hit_key = (unsigned long long*)(b + L.keys);
+    ww.W.dq_e = (float4*)(b + L.entries);
+    ww.W.shadow_state = (int*)(b + L.states);
+    ww.W.dq_cap = (int)L.cap;
+    ww.dq_shape = sh;
     return RTG_OK;
 }
 
@@ -909,7 +840,7 @@ static int last_pass_samples(const rtg::RenderParams& P) {
 
 static int launch(rtg_scene* s, const rtg_render_opts* o, const rtg::DevCamera& C, const rtg::RenderParams& P0,
                   float* d_hdr, uint8_t* d_ldr, float* d_accum, hipStream_t stream) {
-    WaveWork& ww = s->work[0];
+    WaveWork& ww = s->work;
     int pipe = pipeline(s, o, C, P0);
     rtg::RenderParams P = P0;
     if ((pipe == PIPE_WAVE || pipe == PIPE_TREE) && !(o->flags & RTG_RENDER_SAMPLE_PASSES)) {
@@ -995,7 +926,7 @@ static int launch(rtg_scene* s, const rtg_render_opts* o, const rtg::DevCamera& 
         if (P.accum_only) W.accum = (float4*)d_accum;
         else if (C.spp > 1) {   // internal accumulator indexed by absolute pixel
             size_t need = (size_t)C.width * C.height;
-            if (need > ww.pixels) {
+            if (need > ww.shape.pixels) {
                 int rc2 = ensure_wave(ww, need, s->num_slots, blocks, one_payload(s), P.slabs > 1);
                 if (rc2) return rc2;
                 W = ww.W;
@@ -1003,7 +934,7 @@ static int launch(rtg_scene* s, const rtg_render_opts* o, const rtg::DevCamera& 
             }
         }
         if ((s->feat & rtg::FEAT_BIGLEAF) && !stats && rtg::defer_leaves()) {
-            rc = ensure_defer(ww, entries, blocks * 256 * std::max(s->num_slots, 1));
+            rc = ensure_defer(ww, entries, blocks * 256 * std::max(s->num_slots, 1), stream);
             if (rc) return rc;
             W.dq_e = ww.W.dq_e;
             W.dq_count = ww.W.dq_count;
@@ -1136,17 +1067,15 @@ int rtg_render(rtg_scene* s, const rtg_render_opts* o, float* hdr_rgb, uint8_t* 
         whole = P.row_begin == 0 && P.row_end == C.height && (n > 1 || P.part_count == 1);
         HIP_TRY(hipSetDevice(r->device));
         const size_t pixels = (size_t)C.width * C.height;
-        if (r->d_pixels < pixels) {
+        if (r->d_ldr.cap < pixels * 3) {
             HIP_TRY(hipStreamSynchronize(r->stream));
-            if (r->d_hdr) { (void)hipFree(r->d_hdr); r->d_hdr = nullptr; }
-            if (r->d_ldr) { (void)hipFree(r->d_ldr); r->d_ldr = nullptr; }
-            r->d_pixels = 0;
-            HIP_TRY(hipMalloc(&r->d_hdr, pixels * 3 * sizeof(float)));
-            HIP_TRY(hipMalloc(&r->d_ldr, pixels * 3));
-            r->d_pixels = pixels;
+            r->d_hdr.release();
+            r->d_ldr.release();
+            HIP_TRY(r->d_hdr.reserve(pixels * 3));
+            HIP_TRY(r->d_ldr.reserve(pixels * 3));
         }
         if (P.num_tiles == 0) continue;
-        rc = launch(r, &ro[i], C, P, r->d_hdr, r->d_ldr, nullptr, r->stream);
+        rc = launch(r, &ro[i], C, P, r->d_hdr.p, r->d_ldr.p, nullptr, r->stream);
         if (rc) return rc;
         HIP_TRY(hipEventRecord(r->done, r->stream));
     }
@@ -1156,7 +1085,7 @@ int rtg_render(rtg_scene* s, const rtg_render_opts* o, float* hdr_rgb, uint8_t* 
     const bool tonemap = cam.has_tonemapper && whole;
     const rtg_tonemap_params tp = {cam.tm_key, cam.tm_burn, cam.tm_saturation, cam.tm_gamma};
     if (tonemap && n == 1) {
-        int rc = rtg_tonemap_device(s->d_hdr, cam.width, cam.height, &tp, s->d_ldr, s->device, s->stream);
+        int rc = rtg_tonemap_device(s->d_hdr.p, cam.width, cam.height, &tp, s->d_ldr.p, s->device, s->stream);
         if (rc) return rc;
     }
     std::vector<float> tmp;
@@ -1167,7 +1096,7 @@ int rtg_render(rtg_scene* s, const rtg_render_opts* o, float* hdr_rgb, uint8_t* 
     }
     for (int i = 0; i < n; ++i) {
         HIP_TRY(hipSetDevice(reps[i]->device));
-        int rc = copy_part(&ro[i], cam.width, cam.height, reps[i]->d_hdr, reps[i]->d_ldr, hdr,
+        int rc = copy_part(&ro[i], cam.width, cam.height, reps[i]->d_hdr.p, reps[i]->d_ldr.p, hdr,
                            (tonemap && n > 1) ? nullptr : ldr_rgb, reps[i]->stream);
         if (rc) return rc;
     }
@@ -1199,9 +1128,6 @@ int rtg_trace_rays_device(rtg_scene* s, const rtg_ray* d_rays, int64_t n, uint32
     return RTG_OK;
 }
 
-// The host-buffer queries' scratch (rtg_scene::q_mem): one slot per kind of buffer
-enum QuerySlot { Q_RAYS, Q_HITS, Q_NORMALS, Q_RADIANCE, Q_PIXEL_IDS, Q_SURFACE, Q_SLOTS };
-static_assert(sizeof(rtg_scene::q_mem) == Q_SLOTS * sizeof(void*), "one scratch buffer per slot");
 // One staged buffer of a call: copied in from `in` before the launch, out to `out` after it
 // (either may be null); bytes == 0: the call does without it
 struct Staged {
@@ -1213,15 +1139,12 @@ struct Staged {
 
 // slot `k` of at least `bytes`
 static int query_scratch(rtg_scene* s, QuerySlot k, size_t bytes) {
-    if (s->q_cap[k] >= bytes) return RTG_OK;
+    if (s->q[k].cap >= bytes) return RTG_OK;
     HIP_TRY(hipStreamSynchronize(s->stream));
-    if (s->q_mem[k]) { (void)hipFree(s->q_mem[k]); s->q_mem[k] = nullptr; }
-    s->q_cap[k] = 0;
-    if (hipMalloc(&s->q_mem[k], bytes) != hipSuccess) {
+    if (s->q[k].reserve(bytes) != hipSuccess) {
         (void)hipGetLastError();
         return set_err(RTG_ERR_NOMEM, "query scratch of %zu bytes", bytes);
     }
-    s->q_cap[k] = bytes;
     return RTG_OK;
 }
 
@@ -1231,14 +1154,14 @@ static int stage(rtg_scene* s, std::initializer_list<Staged> bufs) {
         if (b.bytes)
             if (int rc = query_scratch(s, b.slot, b.bytes)) return rc;
     for (const Staged& b : bufs)
-        if (b.bytes && b.in) HIP_TRY(hipMemcpyAsync(s->q_mem[b.slot], b.in, b.bytes, hipMemcpyHostToDevice, s->stream));
+        if (b.bytes && b.in) HIP_TRY(hipMemcpyAsync(s->q[b.slot].p, b.in, b.bytes, hipMemcpyHostToDevice, s->stream));
     return RTG_OK;
 }
 
 // the copies out, then the stream's end
 static int unstage(rtg_scene* s, std::initializer_list<Staged> bufs) {
     for (const Staged& b : bufs)
-        if (b.bytes && b.out) HIP_TRY(hipMemcpyAsync(b.out, s->q_mem[b.slot], b.bytes, hipMemcpyDeviceToHost, s->stream));
+        if (b.bytes && b.out) HIP_TRY(hipMemcpyAsync(b.out, s->q[b.slot].p, b.bytes, hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
     return RTG_OK;
 }
@@ -1253,8 +1176,8 @@ int rtg_trace_rays(rtg_scene* s, const rtg_ray* rays, int64_t n, uint32_t flags,
                            {Q_HITS, N * sizeof(rtg_hit), nullptr, hits},
                            {Q_NORMALS, normals ? N * 4 * sizeof(float) : 0, nullptr, normals}};
     if ((rc = stage(s, bufs))) return rc;
-    HIP_TRY(rtg::launch_query(s->ds, s->feat, (rtg_ray*)s->q_mem[Q_RAYS], (int)n, flags, (rtg_hit*)s->q_mem[Q_HITS],
-                              normals ? (float4*)s->q_mem[Q_NORMALS] : nullptr, s->stream));
+    HIP_TRY(rtg::launch_query(s->ds, s->feat, (rtg_ray*)s->q[Q_RAYS].p, (int)n, flags, (rtg_hit*)s->q[Q_HITS].p,
+                              normals ? (float4*)s->q[Q_NORMALS].p : nullptr, s->stream));
     return unstage(s, bufs);
 }
 
@@ -1291,7 +1214,7 @@ int rtg_camera_rays(rtg_scene* s, const rtg_render_opts* o, rtg_ray* rays) {
     const std::initializer_list<Staged> bufs = {{Q_RAYS, (size_t)(re - rb) * C.width * sizeof(rtg_ray), nullptr, rays}};
     if ((rc = stage(s, bufs))) return rc;
     HIP_TRY(rtg::launch_camera_rays(C, rb, re, o->sample_begin < 0 ? 0 : o->sample_begin, o->seed,
-                                    (rtg_ray*)s->q_mem[Q_RAYS], s->stream));
+                                    (rtg_ray*)s->q[Q_RAYS].p, s->stream));
     return unstage(s, bufs);
 }
 
@@ -1324,8 +1247,8 @@ int rtg_surface_rays(rtg_scene* s, const rtg_ray* rays, int64_t n, uint32_t flag
     const std::initializer_list<Staged> bufs = {{Q_RAYS, N * sizeof(rtg_ray), rays, nullptr},
                                                 {Q_SURFACE, N * sizeof(rtg_surface), nullptr, out}};
     if ((rc = stage(s, bufs))) return rc;
-    HIP_TRY(rtg::launch_surface(s->ds, s->shade_sk, s->feat, (rtg_ray*)s->q_mem[Q_RAYS], (int)n, flags,
-                                (rtg_surface*)s->q_mem[Q_SURFACE], s->stream));
+    HIP_TRY(rtg::launch_surface(s->ds, s->shade_sk, s->feat, (rtg_ray*)s->q[Q_RAYS].p, (int)n, flags,
+                                (rtg_surface*)s->q[Q_SURFACE].p, s->stream));
     return unstage(s, bufs);
 }
 
@@ -1381,8 +1304,8 @@ int rtg_radiance_rays(rtg_scene* s, const rtg_radiance_opts* o, const rtg_ray* r
                            {Q_RADIANCE, N * 4 * sizeof(float), nullptr, rgbt},
                            {Q_PIXEL_IDS, pixel_ids ? N * sizeof(int32_t) : 0, pixel_ids, nullptr}};
     if ((rc = stage(s, bufs))) return rc;
-    HIP_TRY(rtg::launch_radiance(s->ds, C, P, s->shade_sk, s->feat, (rtg_ray*)s->q_mem[Q_RAYS],
-                                 pixel_ids ? (int32_t*)s->q_mem[Q_PIXEL_IDS] : nullptr, (float*)s->q_mem[Q_RADIANCE],
+    HIP_TRY(rtg::launch_radiance(s->ds, C, P, s->shade_sk, s->feat, (rtg_ray*)s->q[Q_RAYS].p,
+                                 pixel_ids ? (int32_t*)s->q[Q_PIXEL_IDS].p : nullptr, (float*)s->q[Q_RADIANCE].p,
                                  s->stream));
     return unstage(s, bufs);
 }
@@ -1441,41 +1364,31 @@ int rtg_tonemap(const float* hdr, int32_t w, int32_t h, const rtg_tonemap_params
     if (!hdr || !ldr || !tp || w <= 0 || h <= 0) return set_err(RTG_ERR_INVALID, "bad tonemap arguments");
     HIP_TRY(hipSetDevice(device));
     const size_t n = (size_t)w * h * 3;
-    float* dh = nullptr;
-    uint8_t* dl = nullptr;
-    HIP_TRY(hipMalloc(&dh, n * sizeof(float)));
-    if (hipMalloc(&dl, n) != hipSuccess) { (void)hipFree(dh); return set_err(RTG_ERR_NOMEM, "device allocation failed"); }
-    int rc = RTG_OK;
-    if (hipMemcpy(dh, hdr, n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) rc = set_err(RTG_ERR_HIP, "copy failed");
-    if (!rc) rc = rtg_tonemap_device(dh, w, h, tp, dl, device, nullptr);
-    if (!rc && hipMemcpy(ldr, dl, n, hipMemcpyDeviceToHost) != hipSuccess) rc = set_err(RTG_ERR_HIP, "copy failed");
-    (void)hipFree(dh);
-    (void)hipFree(dl);
-    return rc;
+    DevBuf<float> dh;
+    DevBuf<uint8_t> dl;
+    HIP_TRY(dh.alloc(n));
+    if (dl.alloc(n) != hipSuccess) return set_err(RTG_ERR_NOMEM, "device allocation failed");
+    if (hipMemcpy(dh.p, hdr, n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return set_err(RTG_ERR_HIP, "copy failed");
+    if (int rc = rtg_tonemap_device(dh.p, w, h, tp, dl.p, device, nullptr)) return rc;
+    if (hipMemcpy(ldr, dl.p, n, hipMemcpyDeviceToHost) != hipSuccess) return set_err(RTG_ERR_HIP, "copy failed");
+    return RTG_OK;
 }
 
 int rtg_tonemap_log_average(const float* hdr, int32_t w, int32_t h, int32_t mode, double* avg_out, int32_t device) {
     if (!hdr || !avg_out || w <= 0 || h <= 0 || mode > 3) return set_err(RTG_ERR_INVALID, "bad log-average arguments");
     HIP_TRY(hipSetDevice(device));
     const size_t n = (size_t)w * h;
-    float* dh = nullptr;
-    void* scratch = nullptr;
-    HIP_TRY(hipMalloc(&dh, 3 * n * sizeof(float)));
-    if (hipMalloc(&scratch, rtg::tonemap_scratch_bytes((long long)n)) != hipSuccess) {
-        (void)hipFree(dh);
+    DevBuf<float> dh;
+    DevBuf<char> scratch;
+    HIP_TRY(dh.alloc(3 * n));
+    if (scratch.alloc(rtg::tonemap_scratch_bytes((long long)n)) != hipSuccess)
         return set_err(RTG_ERR_NOMEM, "device allocation failed");
-    }
-    int rc = RTG_OK;
-    if (hipMemcpy(dh, hdr, 3 * n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) rc = set_err(RTG_ERR_HIP, "copy failed");
-    if (!rc) {
-        rtg::launch_log_average(dh, (long long)n, mode, 0, scratch, nullptr);
-        if (hipGetLastError() != hipSuccess ||
-            hipMemcpy(avg_out, (char*)scratch + rtg::tonemap_avg_offset(), sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
-            rc = set_err(RTG_ERR_HIP, "log-average failed");
-    }
-    (void)hipFree(dh);
-    (void)hipFree(scratch);
-    return rc;
+    if (hipMemcpy(dh.p, hdr, 3 * n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return set_err(RTG_ERR_HIP, "copy failed");
+    rtg::launch_log_average(dh.p, (long long)n, mode, 0, scratch.p, nullptr);
+    if (hipGetLastError() != hipSuccess ||
+        hipMemcpy(avg_out, scratch.p + rtg::tonemap_avg_offset(), sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+        return set_err(RTG_ERR_HIP, "log-average failed");
+    return RTG_OK;
 }
 
 int rtg_resolve_accum(const float* accum, int32_t w, int32_t h, float* hdr, uint8_t* ldr) {

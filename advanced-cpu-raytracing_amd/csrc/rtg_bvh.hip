@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "rtg_common.hpp"
+#include "rtg_devmem.hpp"
 #include "rtg_kernels.hpp"
 
 namespace rtg {
@@ -313,7 +314,7 @@ inline int nblk(long long n) { return (int)((n + 255) / 256); }
 #define BVH_TRY(x)                                \
     do {                                          \
         hipError_t e_ = (x);                      \
-        if (e_ != hipSuccess) { cleanup(); return e_; } \
+        if (e_ != hipSuccess) return e_;          \
     } while (0)
 
 hipError_t build_mesh_bvh(const rtg_face* d_faces, int n, const float root_mn[3], const float root_mx[3],
@@ -322,12 +323,14 @@ hipError_t build_mesh_bvh(const rtg_face* d_faces, int n, const float root_mn[3]
                           hipStream_t st) {
     BvhTmp T;
     std::memset(&T, 0, sizeof(T));
-    std::vector<void*> allocs;
-    auto cleanup = [&]() { for (void* p : allocs) (void)hipFree(p); };
+    std::vector<DevBuf<char>> tmp;            // T's arrays, 16 spare bytes each; freed on return
+    auto bytes = [&](size_t n) -> hipError_t {
+        tmp.emplace_back();
+        return tmp.back().reserve(n, [](size_t) { return (size_t)16; });
+    };
     auto alloc = [&](auto*& p, size_t count) -> hipError_t {
-        void* q = nullptr;
-        hipError_t e = hipMalloc(&q, count * sizeof(*p) + 16);
-        if (e == hipSuccess) { allocs.push_back(q); p = (std::remove_reference_t<decltype(p)>)q; }
+        hipError_t e = bytes(count * sizeof(*p));
+        p = (std::remove_reference_t<decltype(p)>)(void*)tmp.back().p;
         return e;
     };
     const size_t N = (size_t)n, NN = 2 * N;   // at most 2n - 1 nodes
@@ -342,8 +345,8 @@ hipError_t build_mesh_bvh(const rtg_face* d_faces, int n, const float root_mn[3]
     BVH_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, sb1, T.big, T.bigscan, n, st));
     BVH_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, sb2, T.dosplit, T.childoff, (int)NN, st));
     T.scan_bytes = sb1 > sb2 ? sb1 : sb2;
-    BVH_TRY(hipMalloc(&T.scan_tmp, T.scan_bytes + 16));
-    allocs.push_back(T.scan_tmp);
+    BVH_TRY(bytes(T.scan_bytes));
+    T.scan_tmp = tmp.back().p;
 
     // root: the mesh bbox (parser.cpp:1393-1468, FLT_MIN max-corner quirk included)
     float rb[6] = {root_mn[0], root_mn[1], root_mn[2], root_mx[0], root_mx[1], root_mx[2]};
@@ -358,8 +361,8 @@ hipError_t build_mesh_bvh(const rtg_face* d_faces, int n, const float root_mn[3]
 
     std::vector<std::pair<int, int>> levels;     // BFS id range per level
     int lo = 0, hi = 1;
-    int* h_split = nullptr;
-    BVH_TRY(hipHostMalloc(&h_split, 2 * sizeof(int)));
+    PinnedBuf<int> h_split;
+    BVH_TRY(h_split.alloc(2));
     while (lo < hi) {
         levels.emplace_back(lo, hi);
         const int m = hi - lo;
@@ -386,7 +389,6 @@ hipError_t build_mesh_bvh(const rtg_face* d_faces, int n, const float root_mn[3]
         lo = hi;
         hi = hi + 2 * nsplit;
     }
-    (void)hipHostFree(h_split);
     const int total = hi;
     for (int L = (int)levels.size() - 1; L >= 0; --L)
         hipLaunchKernelGGL(k_size, dim3(nblk(levels[L].second - levels[L].first)), dim3(256), 0, st, T,
@@ -405,7 +407,6 @@ hipError_t build_mesh_bvh(const rtg_face* d_faces, int n, const float root_mn[3]
     BVH_TRY(hipStreamSynchronize(st));
     *nodeCount = total;
     *bigleaf = bl != 0;
-    cleanup();
     return hipSuccess;
 }
 

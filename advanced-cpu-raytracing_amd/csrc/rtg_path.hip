@@ -49,6 +49,7 @@
 #include <vector>
 
 #include "rtg_common.hpp"
+#include "rtg_devmem.hpp"
 #include "rtg_kernels.hpp"
 #include "rtg_node.hpp"
 
@@ -334,18 +335,24 @@ __global__ void k_path_check(int* cnt, int last_it) {
 // ---------------------------------------------------------------------------
 // Host side
 // ---------------------------------------------------------------------------
+// the buffers behind PathBufs
+struct PathMem {
+    DevBuf<float4> ro, rd, tp, frames;
+    DevBuf<unsigned long long> key;
+    DevBuf<int> act0, act1, cnt, hobj, hface;
+    DevBuf<float> ht;
+};
+
 struct PathState {
     PathBufs B{};
+    PathMem mem;
     size_t cap = 0;                 // paths the buffers hold
     int levels = 0;                 // frame levels the buffers hold
-    int* h = nullptr;               // pinned host words: [0] a queue size, [1] the overflow flag
+    PinnedBuf<int> h;               // pinned host words: [0] a queue size, [1] the overflow flag
     std::vector<int> plan;          // grid paths per iteration of planned passes
     std::vector<long long> plan_key;
-    ~PathState() { release(); if (h) (void)hipHostFree(h); }
     void release() {
-        auto f = [](void* p) { if (p) (void)hipFree(p); };
-        f(B.ro); f(B.rd); f(B.key); f(B.tp); f(B.frames); f(B.act0); f(B.act1); f(B.cnt); f(B.ht); f(B.hobj);
-        f(B.hface);
+        mem = PathMem{};
         B = PathBufs{};
         cap = 0;
         levels = 0;
@@ -359,20 +366,24 @@ static hipError_t ensure_paths(PathState& T, size_t n, int levels) {
     n = std::max(n, T.cap);
     levels = std::max(levels, T.levels);
     T.release();
-    hipError_t e;
+    PathMem& M = T.mem;
+    PathBufs& B = T.B;
+    hipError_t e = hipSuccess;
+    auto alloc = [&e](auto& buf, auto*& ptr, size_t count) {
+        if (e == hipSuccess) e = buf.alloc(count);
+        ptr = buf.p;
+    };
+    alloc(M.ro, B.ro, n); alloc(M.rd, B.rd, n); alloc(M.key, B.key, n); alloc(M.tp, B.tp, n);
+    alloc(M.frames, B.frames, n * (size_t)levels * kFrameChunks);
+    alloc(M.act0, B.act0, n); alloc(M.act1, B.act1, n); alloc(M.cnt, B.cnt, kPathMaxIter + 2);
+    alloc(M.ht, B.ht, n); alloc(M.hobj, B.hobj, n); alloc(M.hface, B.hface, n);
     // an allocation that fails leaves the render to the fused kernel (hipErrorNotSupported)
-#define A_(ptr, bytes)                                  \
-    if ((e = hipMalloc(&ptr, bytes)) != hipSuccess) {   \
-        (void)hipGetLastError();                        \
-        T.release();                                    \
-        return hipErrorNotSupported;                    \
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        T.release();
+        return hipErrorNotSupported;
     }
-    A_(T.B.ro, n * 16); A_(T.B.rd, n * 16); A_(T.B.key, n * 8); A_(T.B.tp, n * 16);
-    A_(T.B.frames, n * (size_t)levels * kFrameChunks * 16);
-    A_(T.B.act0, n * 4); A_(T.B.act1, n * 4); A_(T.B.cnt, (kPathMaxIter + 2) * sizeof(int));
-    A_(T.B.ht, n * 4); A_(T.B.hobj, n * 4); A_(T.B.hface, n * 4);
-#undef A_
-    T.B.cap = (int)n;
+    B.cap = (int)n;
     T.cap = n;
     T.levels = levels;
     return hipSuccess;
@@ -429,7 +440,7 @@ static hipError_t path_pass(PathState& T, const PathKernels& K, const DevScene& 
         for (int it = 0;; ++it) {
             if (it >= path_iter_cap()) return hipErrorNotSupported;   // the fused kernel takes the render
             iteration(it, paths);
-            if ((e = hipMemcpyAsync(T.h, B.cnt + it + 1, sizeof(int), hipMemcpyDeviceToHost, st)) != hipSuccess)
+            if ((e = hipMemcpyAsync(T.h.p, B.cnt + it + 1, sizeof(int), hipMemcpyDeviceToHost, st)) != hipSuccess)
                 return e;
             if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;
             paths = T.h[0];
@@ -457,7 +468,7 @@ static hipError_t path_run(PathState& T, const PathKernels& K, bool stats, const
                            const RenderParams& P, int maxd, float* hdr, unsigned char* l, float4* accum,
                            DevCounters* cnt, hipStream_t st, hipEvent_t* ev) {
     hipError_t e;
-    if (!T.h && (e = hipHostMalloc(&T.h, 4 * sizeof(int))) != hipSuccess) return e;
+    if (!T.h.p && (e = T.h.alloc(4)) != hipSuccess) return e;
     const int npix = P.part_rows * C.width;
     // paths per pass: up to 2^20, and at most half the device memory free now (the frame stacks:
     // 208 B x maxd levels per path -- 6.9 GB at 2^20 paths x 32 levels)
@@ -532,7 +543,7 @@ static hipError_t path_run(PathState& T, const PathKernels& K, bool stats, const
         }
         if (!any_planned) return hipSuccess;
         // one synchronisation per render: did a planned pass leave paths unfinished?
-        if ((e = hipMemcpyAsync(T.h + 1, T.B.cnt + kPathMaxIter + 1, sizeof(int), hipMemcpyDeviceToHost, st)) !=
+        if ((e = hipMemcpyAsync(T.h.p + 1, T.B.cnt + kPathMaxIter + 1, sizeof(int), hipMemcpyDeviceToHost, st)) !=
             hipSuccess)
             return e;
         if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;

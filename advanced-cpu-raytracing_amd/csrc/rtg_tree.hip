@@ -24,9 +24,11 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <vector>
 
 #include "rtg_common.hpp"
+#include "rtg_devmem.hpp"
 #include "rtg_kernels.hpp"
 
 namespace rtg {
@@ -504,72 +506,63 @@ __global__ __launch_bounds__(256) void k_tree_accum(const DevCamera C, const Ren
 // ---------------------------------------------------------------------------
 // Host side
 // ---------------------------------------------------------------------------
-namespace {
-
-template <typename T>
-hipError_t grow(T*& p, size_t& cap, size_t n) {
-    if (n <= cap) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    const size_t want = n + n / 4 + 1024;
-    hipError_t e = hipMalloc(&p, want * sizeof(T));
-    if (e == hipSuccess) cap = want;
-    return e;
-}
-
-}  // namespace
-
 struct TreeState {
+    // a level's arrays, and the kernels' view of them (ensure_level)
     struct Level {
         TreeLevel L{};
-        size_t cap = 0, cap_slots = 0;
-        // separate capacities per array (grown together)
-        size_t co = 0, cd = 0, ck = 0, cm = 0, ct = 0, cob = 0, cf = 0, cb = 0, cc = 0, ce = 0, cv = 0, cte = 0, coc = 0;
+        DevBuf<float4> o, d, miss, base, coef, ext, value, term;
+        DevBuf<unsigned long long> key;
+        DevBuf<float> t;
+        DevBuf<int> obj, face;
+        DevBuf<unsigned char> occ;
     };
     std::vector<Level> levels;
+    // the blocks' output segments and their scanned offsets, and the kernels' view (ensure_segs)
     TreeSegs G{};
-    size_t c_qo = 0, c_qd = 0, c_qs = 0, c_qc = 0, c_o = 0, c_d = 0, c_k = 0, c_m = 0, c_p = 0, c_cc = 0, c_off = 0;
-    int* offs = nullptr;
-    int* h_total = nullptr;     // pinned host words: [0] a level's size, [1..4] the streams' overflow flags
+    DevBuf<float4> q_o, q_d, c_o, c_d, c_miss;
+    DevBuf<unsigned long long> c_key;
+    DevBuf<int> q_slot, q_count, c_parent, c_count, offs;
+    PinnedBuf<int> h_total;     // pinned host words: [0] a level's size, [1..4] the streams' overflow flags
     // device-driven levels: per level the ray count (written by the previous level's scan) and
     // the overflow flag; the plan = capacities per level learned from a host-driven pass of
     // the same frame part (plan_key)
-    int* d_counts = nullptr;    // kMaxLevels + 1 ints, [kMaxLevels] = overflow
+    DevBuf<int> d_counts;       // kMaxLevels + 1 ints, [kMaxLevels] = overflow
     std::vector<size_t> plan;
     std::vector<long long> plan_key;
     int sk = SK_ALL;            // the scene's shading features (k_tree_shade variant)
     // multi-stream planned passes (tree_streams): the other streams' level buffers and the
     // streams; fork / join events and two "resolve done" events (sample order of the resolves)
-    std::vector<TreeState*> twins;
+    std::vector<std::unique_ptr<TreeState>> twins;
     std::vector<hipStream_t> xst;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_res[2] = {nullptr, nullptr};
     ~TreeState() {
-        for (TreeState* t : twins) delete t;
+        twins.clear();
         for (hipStream_t x : xst) (void)hipStreamDestroy(x);
         for (hipEvent_t e : {ev_fork, ev_join, ev_res[0], ev_res[1]})
             if (e) (void)hipEventDestroy(e);
-        auto f = [](void* p) { if (p) (void)hipFree(p); };
-        for (auto& lv : levels) {
-            TreeLevel& L = lv.L;
-            f(L.o); f(L.d); f(L.key); f(L.miss); f(L.t); f(L.obj); f(L.face); f(L.base); f(L.coef); f(L.ext);
-            f(L.value); f(L.term); f(L.occ);
-        }
-        f(G.q_o); f(G.q_d); f(G.q_slot); f(G.q_count); f(G.c_o); f(G.c_d); f(G.c_key); f(G.c_miss); f(G.c_parent);
-        f(G.c_count); f(offs); f(d_counts);
-        if (h_total) (void)hipHostFree(h_total);
     }
 };
 constexpr int kMaxLevels = 64;
 
+// Grows `buf` to `n` entries (with a quarter and 1 024 entries of slack: levels vary from pass
+// to pass) and hands the kernels its pointer; after a failure nothing more is attempted.
+static size_t tree_slack(size_t n) { return n / 4 + 1024; }
+template <typename T>
+static void grown(hipError_t& e, DevBuf<T>& buf, T*& ptr, size_t n) {
+    if (e != hipSuccess) return;
+    e = buf.reserve(n, tree_slack);
+    ptr = buf.p;
+}
+
 static hipError_t ensure_level(TreeState::Level& lv, size_t n, int ns) {
     TreeLevel& L = lv.L;
-    hipError_t e;
-#define G_(ptr, c, cnt) if ((e = grow(ptr, lv.c, cnt)) != hipSuccess) return e
-    G_(L.o, co, n); G_(L.d, cd, n); G_(L.key, ck, n); G_(L.miss, cm, n); G_(L.t, ct, n); G_(L.obj, cob, n);
-    G_(L.face, cf, n); G_(L.base, cb, n); G_(L.coef, cc, n); G_(L.ext, ce, n); G_(L.value, cv, n);
-    G_(L.term, cte, n * (size_t)(ns > 0 ? ns : 1)); G_(L.occ, coc, n * (size_t)(ns > 0 ? ns : 1));
-#undef G_
+    const size_t nt = n * (size_t)(ns > 0 ? ns : 1);
+    hipError_t e = hipSuccess;
+    grown(e, lv.o, L.o, n); grown(e, lv.d, L.d, n); grown(e, lv.key, L.key, n); grown(e, lv.miss, L.miss, n);
+    grown(e, lv.t, L.t, n); grown(e, lv.obj, L.obj, n); grown(e, lv.face, L.face, n); grown(e, lv.base, L.base, n);
+    grown(e, lv.coef, L.coef, n); grown(e, lv.ext, L.ext, n); grown(e, lv.value, L.value, n);
+    grown(e, lv.term, L.term, nt); grown(e, lv.occ, L.occ, nt);
+    if (e != hipSuccess) return e;
     L.n = (int)n;
     L.nd = nullptr;
     return hipSuccess;
@@ -577,13 +570,15 @@ static hipError_t ensure_level(TreeState::Level& lv, size_t n, int ns) {
 
 static hipError_t ensure_segs(TreeState& T, size_t blocks, int ns) {
     TreeSegs& G = T.G;
-    hipError_t e;
     const size_t nq = blocks * 256 * (size_t)(ns > 0 ? ns : 1), nc = blocks * 512;
-#define G_(ptr, c, cnt) if ((e = grow(ptr, T.c, cnt)) != hipSuccess) return e
-    G_(G.q_o, c_qo, nq); G_(G.q_d, c_qd, nq); G_(G.q_slot, c_qs, nq); G_(G.q_count, c_qc, blocks);
-    G_(G.c_o, c_o, nc); G_(G.c_d, c_d, nc); G_(G.c_key, c_k, nc); G_(G.c_miss, c_m, nc); G_(G.c_parent, c_p, nc);
-    G_(G.c_count, c_cc, blocks); G_(T.offs, c_off, blocks + 1);
-#undef G_
+    hipError_t e = hipSuccess;
+    grown(e, T.q_o, G.q_o, nq); grown(e, T.q_d, G.q_d, nq); grown(e, T.q_slot, G.q_slot, nq);
+    grown(e, T.q_count, G.q_count, blocks);
+    grown(e, T.c_o, G.c_o, nc); grown(e, T.c_d, G.c_d, nc); grown(e, T.c_key, G.c_key, nc);
+    grown(e, T.c_miss, G.c_miss, nc); grown(e, T.c_parent, G.c_parent, nc);
+    grown(e, T.c_count, G.c_count, blocks);
+    if (e == hipSuccess) e = T.offs.reserve(blocks + 1, tree_slack);
+    if (e != hipSuccess) return e;
     G.num_slots = ns;
     return hipSuccess;
 }
@@ -613,8 +608,8 @@ static void level_launches(TreeState& T, const DevScene& S, const DevCamera& C, 
         W.hit_face = L.face;
         hipLaunchKernelGGL((k_shadow<STATS, FEAT, false>), dim3(blocks, ns), dim3(256), 0, st, S, W, cnt);
     }
-    hipLaunchKernelGGL(k_tree_scan, dim3(1), dim3(1024), 0, st, T.G.c_count, blocks, T.offs, next_n, cap_next,
-                       T.d_counts ? T.d_counts + kMaxLevels : nullptr);
+    hipLaunchKernelGGL(k_tree_scan, dim3(1), dim3(1024), 0, st, T.G.c_count, blocks, T.offs.p, next_n, cap_next,
+                       T.d_counts.p ? T.d_counts.p + kMaxLevels : nullptr);
 }
 
 // Host-driven sample pass: after each level the next level's size comes back to the host
@@ -638,16 +633,16 @@ static hipError_t tree_pass_sync(TreeState& T, const DevScene& S, const DevCamer
         const int blocks = (int)((n + 255) / 256);
         if ((e = ensure_segs(T, (size_t)blocks, ns)) != hipSuccess) return e;
         level_launches<STATS, FEAT>(T, S, C, P, s, level, L, blocks, ns, nullptr, 0, cnt, st);
-        if ((e = hipMemcpyAsync(T.h_total, T.offs + blocks, sizeof(int), hipMemcpyDeviceToHost, st)) != hipSuccess)
+        if ((e = hipMemcpyAsync(T.h_total.p, T.offs.p + blocks, sizeof(int), hipMemcpyDeviceToHost, st)) != hipSuccess)
             return e;
         if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;
-        const size_t nn = (size_t)*T.h_total;
+        const size_t nn = (size_t)T.h_total[0];
         if (nn == 0) break;
         if (level + 1 >= kMaxLevels) return hipErrorInvalidValue;
         sizes.push_back(nn);
         if ((int)T.levels.size() <= level + 1) T.levels.emplace_back();
         if ((e = ensure_level(T.levels[level + 1], nn, ns)) != hipSuccess) return e;
-        hipLaunchKernelGGL(k_tree_compact, dim3(blocks), dim3(256), 0, st, T.G, T.offs, T.levels[level].L,
+        hipLaunchKernelGGL(k_tree_compact, dim3(blocks), dim3(256), 0, st, T.G, T.offs.p, T.levels[level].L,
                            T.levels[level + 1].L, (int)nn);
         n = nn;
     }
@@ -684,16 +679,16 @@ static hipError_t tree_pass_async(TreeState& T, const DevScene& S, const DevCame
     for (int level = 0; level < D; ++level) {
         TreeLevel& L = T.levels[level].L;
         L.n = (int)T.plan[level];
-        L.nd = level == 0 ? nullptr : T.d_counts + level;
+        L.nd = level == 0 ? nullptr : T.d_counts.p + level;
         const int blocks = (int)((T.plan[level] + 255) / 256);
         const bool more = level + 1 < D;
-        level_launches<STATS, FEAT>(T, S, C, P, s, level, L, blocks, ns, T.d_counts + level + 1,
+        level_launches<STATS, FEAT>(T, S, C, P, s, level, L, blocks, ns, T.d_counts.p + level + 1,
                                     more ? (int)T.plan[level + 1] : 0, cnt, st);
         if (more) {
             TreeLevel& Ln = T.levels[level + 1].L;
             Ln.n = (int)T.plan[level + 1];
-            Ln.nd = T.d_counts + level + 1;
-            hipLaunchKernelGGL(k_tree_compact, dim3(blocks), dim3(256), 0, st, T.G, T.offs, L, Ln,
+            Ln.nd = T.d_counts.p + level + 1;
+            hipLaunchKernelGGL(k_tree_compact, dim3(blocks), dim3(256), 0, st, T.G, T.offs.p, L, Ln,
                                (int)T.plan[level + 1]);
         }
     }
@@ -736,9 +731,9 @@ template <bool STATS, int FEAT>
 static hipError_t tree_run(TreeState& T, const DevScene& S, const DevCamera& C, const RenderParams& P, float* hdr,
                            unsigned char* l, float4* accum, DevCounters* cnt, hipStream_t st, hipEvent_t* ev) {
     hipError_t e;
-    if (!T.h_total) {
-        if ((e = hipHostMalloc(&T.h_total, 8 * sizeof(int))) != hipSuccess) return e;
-        if ((e = hipMalloc(&T.d_counts, (kMaxLevels + 1) * sizeof(int))) != hipSuccess) return e;
+    if (!T.h_total.p) {
+        if ((e = T.h_total.alloc(8)) != hipSuccess) return e;
+        if ((e = T.d_counts.alloc(kMaxLevels + 1)) != hipSuccess) return e;
     }
     const int ns = S.num_point + S.num_area + S.num_env + S.num_dir + S.num_spot + S.num_mesh;
     // the plan belongs to one frame part of one camera (its view and samples decide the level
@@ -755,7 +750,7 @@ static hipError_t tree_run(TreeState& T, const DevScene& S, const DevCamera& C, 
         }
         if ((r = ensure_segs(U, (*std::max_element(U.plan.begin(), U.plan.end()) + 255) / 256, ns)) != hipSuccess)
             return r;
-        return hipMemsetAsync(U.d_counts + kMaxLevels, 0, sizeof(int), st);
+        return hipMemsetAsync(U.d_counts.p + kMaxLevels, 0, sizeof(int), st);
     };
     auto prepare = [&]() -> hipError_t {
         hipError_t r;
@@ -767,11 +762,11 @@ static hipError_t tree_run(TreeState& T, const DevScene& S, const DevCamera& C, 
             hipStream_t x;
             if ((r = hipStreamCreateWithFlags(&x, hipStreamNonBlocking)) != hipSuccess) return r;
             T.xst.push_back(x);
-            T.twins.push_back(new TreeState());
+            T.twins.push_back(std::make_unique<TreeState>());
         }
         for (int k = 0; k < NS - 1; ++k) {
             TreeState& U = *T.twins[k];
-            if (!U.d_counts && (r = hipMalloc(&U.d_counts, (kMaxLevels + 1) * sizeof(int))) != hipSuccess) return r;
+            if (!U.d_counts.p && (r = U.d_counts.alloc(kMaxLevels + 1)) != hipSuccess) return r;
             U.sk = T.sk;
             U.plan = T.plan;
             U.plan_key = T.plan_key;
@@ -859,7 +854,7 @@ static hipError_t tree_run(TreeState& T, const DevScene& S, const DevCamera& C, 
         // one synchronisation per render: did a level outgrow the plan (on any stream's buffers)?
         const int nf = used2 ? NS : 1;
         for (int k = 0; k < nf; ++k)
-            if ((e = hipMemcpyAsync(T.h_total + 1 + k, (k ? T.twins[k - 1]->d_counts : T.d_counts) + kMaxLevels,
+            if ((e = hipMemcpyAsync(T.h_total.p + 1 + k, (k ? T.twins[k - 1]->d_counts : T.d_counts).p + kMaxLevels,
                                     sizeof(int), hipMemcpyDeviceToHost, st)) != hipSuccess)
                 return e;
         if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;

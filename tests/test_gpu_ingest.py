@@ -56,6 +56,17 @@ def test_device_bvh_equals_host_bvh(name):
     assert ds_h.stats() == ds_d.stats()
 
 
+def test_device_bvh_built_twice():
+    """The build's temporaries are freed on return: a second build of the same mesh in the same
+    process, beside the first scene, gives the host-built records again."""
+    hs, hd, ds_h, ds_d = _pair("simple.xml")
+    ds_d2 = rtgpu.DeviceScene(hd, 0)
+    assert _same_bvh(ds_h, ds_d) == _same_bvh(ds_h, ds_d2)
+    ds_d.close()
+    ds_d3 = rtgpu.DeviceScene(hd, 0)
+    _same_bvh(ds_h, ds_d3)
+
+
 @pytest.mark.parametrize("K", [100352, 869558])
 def test_device_bvh_full_size(tmp_path, K):
     """The headline height field and a C5-size (870k-triangle) mesh."""
