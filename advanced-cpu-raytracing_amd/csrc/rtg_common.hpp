@@ -1078,11 +1078,13 @@ DEV bool sphere_t(const DevObject& ob, const Ray& lr, float minT, float& tout) {
     return t < minT && t > 0.0f;
 }
 
+// MOTION = false: the caller never meets a motion-blurred object (surface())
+template <bool MOTION = true>
 DEV Ray local_ray(const DevObject& ob, const Ray& r, float mbTime) {
     Ray lr;
     lr.o = xform(ob.inv, r.o, 1.0f);
     lr.d = xform(ob.inv, r.d, 0.0f);
-    if (ob.flags & OBJF_MOTION_BLUR) lr.o = add(lr.o, muls(ld3(ob.mbv), mbTime));
+    if (MOTION && (ob.flags & OBJF_MOTION_BLUR)) lr.o = add(lr.o, muls(ld3(ob.mbv), mbTime));
     return lr;
 }
 // Traversal-only variant: an exact identity transform changes at most the sign of a zero
@@ -1734,7 +1736,11 @@ DEV f3 mesh_mapped_normal(const DevScene& S, const DevObject& ob, int face, f3 l
 DEV f3 sphere_bumped_normal(const DevScene& S, const DevObject& ob, f3 p, float phi, float theta, float u, float v);
 
 // MAPS = false: the scene has no normal / bump maps (OBJF_MAPPED never set; k_shade variants)
-template <bool STATS, bool MAPS = true>
+// FEAT: the scene's feature bits where the caller's variant knows them (k_shade's fused layouts;
+// FEAT_ALL: any scene): without FEAT_SPHERE no hit is a sphere's and that branch is compiled out.
+// MOTION = false: the caller's pipeline never renders a scene with motion blur (k_shade), so
+// OBJF_MOTION_BLUR is not tested and mbTime not read.
+template <bool STATS, bool MAPS = true, int FEAT = FEAT_ALL, bool MOTION = true>
 DEV Surf surface(const DevScene& S, const Ray& r, float mbTime, const Hit& h, Cnt<STATS>& c) {
     const DevObject& ob = S.objects[GIDX(S, h.obj, S.num_objects, 0)];
     Surf s;
@@ -1743,8 +1749,8 @@ DEV Surf surface(const DevScene& S, const Ray& r, float mbTime, const Hit& h, Cn
     Ray hr;
     hr.o = h.o;
     hr.d = r.d;
-    Ray lr = local_ray(ob, hr, mbTime);
-    if (h.face < 0) {                                                  // sphere.cpp:71-175
+    Ray lr = local_ray<MOTION>(ob, hr, mbTime);
+    if ((FEAT & FEAT_SPHERE) && h.face < 0) {                          // sphere.cpp:71-175
         const f3 center = mk(ob.center[0], ob.center[1], ob.center[2]);
         f3 lp = add(lr.o, muls(lr.d, h.t));
         f3 p = sub(lp, center);
@@ -2372,6 +2378,9 @@ DEV f3 beer(float x, const float* c, f3 L0) {                          // raytra
 
 
 // GenerateRay (raytracer.cpp:661-699) + Camera::GetImagePlanePosition (camera.cpp:74-80)
+// MOTION = false (k_shade: the wavefront pipeline never renders a scene with motion blur): the
+// motion-blur time is not drawn, mbTime = 0
+template <bool MOTION = true>
 DEV Ray camera_ray(const DevCamera& C, int px, int py, uint64_t key, float& mbTime) {
     const f3 q = ld3(C.q), right = ld3(C.right), up = ld3(C.up), cpos = ld3(C.pos);
     float su = (float)((px + 0.5) * (double)(C.right_ext - C.left) / C.width);
@@ -2393,7 +2402,7 @@ DEV Ray camera_ray(const DevCamera& C, int px, int py, uint64_t key, float& mbTi
     } else {
         ray.d = makeUnit(sub(ipp, ray.o));
     }
-    mbTime = rnd(key, RP_MOTION, 0);
+    mbTime = MOTION ? rnd(key, RP_MOTION, 0) : 0.f;
     return ray;
 }
 

@@ -404,15 +404,29 @@ __global__ __launch_bounds__(256, MODE >= SH_FUSED ? (FAST ? RTG_WIDE_WAVES(FEAT
     const int i = valid ? work_index(P, C.width, slab, crow, px) : 0;
     const uint64_t key = root_key(P.seed, pixel, sample);
     static_assert(!FRAME || MODE >= SH_FUSED, "the frame kernel is the fused layout's");
+    // The scene's feature bits as far as this instantiation knows them: the fused layouts are
+    // instantiated per traversal variant, the queued ones (FEAT left at 0) serve every scene.
+    constexpr int SFEAT = MODE >= SH_FUSED ? FEAT : FEAT_ALL;
+    // No scene with a motion-blurred object reaches this pipeline (scene_tables.cpp scene_scalars:
+    // wave_ok = !blur, recomputed by every update; rtg_api.cpp pipeline() takes the wavefront
+    // kernels only with wave_ok), so no k_shade instantiation draws the motion-blur time or tests
+    // OBJF_MOTION_BLUR in surface(); the walks are handed mbTime = 0 and never use it.
+    constexpr bool MOTION = false;
     Hit fh;                          // FRAME: the camera ray's hit
     fh.obj = -1;
+    // FRAME: the pixel's camera ray, generated once and used by the walk and by shading (trace
+    // takes its ray by reference -- it moves a motion-blurred instance's origin, which cannot
+    // happen here -- so it gets a copy and shading keeps the ray as generated)
+    Ray ray;
+    ray.o = ray.d = mk(0, 0, 0);
+    float mbTime = 0.f;
     if constexpr (FRAME) {
         if (valid) {
-            float mbt;
-            Ray cr = camera_ray(C, px, py, key, mbt);
+            ray = camera_ray<MOTION>(C, px, py, key, mbTime);
             cn.cam();
-            trace<false, STATS, FEAT, RTG_PRIMARY_PACKET != 0 && !(FEAT & FEAT_BIGLEAF)>(S, cr, mbt, INFINITY, INFINITY,
-                                                                                           fh, cn);
+            Ray cr = ray;
+            trace<false, STATS, FEAT, RTG_PRIMARY_PACKET != 0 && !(FEAT & FEAT_BIGLEAF)>(S, cr, mbTime, INFINITY,
+                                                                                           INFINITY, fh, cn);
         }
     }
     const int obj = FRAME ? fh.obj : (valid ? W.hit_obj[i] : -1);
@@ -438,8 +452,7 @@ __global__ __launch_bounds__(256, MODE >= SH_FUSED ? (FAST ? RTG_WIDE_WAVES(FEAT
         else W.base[i] = make_float4(col.x, col.y, col.z, __int_as_float(flags));
     };
     if (valid) {
-        float mbTime;
-        Ray ray = camera_ray(C, px, py, key, mbTime);
+        if constexpr (!FRAME) ray = camera_ray<MOTION>(C, px, py, key, mbTime);
         if (obj < 0) {
             put_base(miss_color<SK>(S, C, px, py, ray.d), BASE_FINAL);
         } else {
@@ -451,7 +464,7 @@ __global__ __launch_bounds__(256, MODE >= SH_FUSED ? (FAST ? RTG_WIDE_WAVES(FEAT
             h.o = ray.o;
             c.ob = &ob;
             c.mat = &S.materials[ob.material];
-            c.s = surface<STATS, (SK & SK_TEX) != 0>(S, ray, mbTime, h, cn);
+            c.s = surface<STATS, (SK & SK_TEX) != 0, SFEAT, MOTION>(S, ray, mbTime, h, cn);
             w_o = makeUnit(sub(ld3(C.pos), c.s.p));
             const DevMaterial& mat = *c.mat;
             if (mat.type == 3) {                                    // Emissive (raytracer.cpp:81-84)
