@@ -905,9 +905,18 @@ DEV uint64_t obj_key(float t, int k, int f) {
     return ((uint64_t)__float_as_uint(t) << 32) | ((uint64_t)(uint32_t)k << 20) | (uint64_t)((uint32_t)f & 0xFFFFFu);
 }
 
-template <bool ANY, bool STATS, bool SC = false, bool DEFER = false>
+// (the closest-hit scalar-record walk without counters: walk_bvh_packet_lx, further down)
+template <bool DEFER>
+DEV bool walk_bvh_packet_lx(const DevScene& S, int begin, int end, const Ray& r, float& minT, int& hitFace,
+                            DeferCtx* dc, int k);
+
+// LX: the caller asks for the leaf-exact walk (trace: the variants whose kernels keep their registers)
+template <bool ANY, bool STATS, bool SC = false, bool DEFER = false, bool LX = false>
 DEV bool walk_bvh_packet(const DevScene& S, int begin, int end, const Ray& r, float& minT, int& hitFace,
                          float limit, Cnt<STATS>& c, DeferCtx* dc = nullptr, int k = 0) {
+    // counting renders (the oracle's node visits), the any-hit form and the vector-load form keep the
+    // walk below, exact at every node
+    if constexpr (LX && SC && !ANY && !STATS) return walk_bvh_packet_lx<DEFER>(S, begin, end, r, minT, hitFace, dc, k);
     // the node range is the object's (wave-uniform): SGPRs, so the loop index and its bound stay
     // scalar; "a face was accepted" is read off hitFace at the end instead of a lane mask kept
     // through every iteration
@@ -1179,9 +1188,15 @@ DEV bool trace(const DevScene& S, Ray& r, float mbTime, float minT, float limit,
         int face = -1;
         float t = h.t;
         bool found;
+        // The leaf-exact walk (walk_bvh_packet_lx) for scenes of plain meshes only.  Its six
+        // conservative constants are live through the walk beside the ray a sphere, an instance or a
+        // transform keeps: with it those variants lose a wave (k_primary, FEAT 15: 71 -> 79 VGPRs) or
+        // gain scratch (FEAT 1: k_primary 0 -> 28 B, k_query 12 -> 64 B; FEAT 7: k_frame 8 -> 20 B), so
+        // they keep the walk that is exact at every node (profiles/r12_resource_lines.txt).
+        constexpr bool LX = !(FEAT & (FEAT_SPHERE | FEAT_INSTANCE | FEAT_XFORM));
         if constexpr (PK)
-            found = walk_bvh_packet<ANY, STATS, RTG_PRIMARY_PACKET == 2, DEFER>(S, ob.node_begin, ob.node_end, lr, t,
-                                                                                  face, limit, c, dc, k);
+            found = walk_bvh_packet<ANY, STATS, RTG_PRIMARY_PACKET == 2, DEFER, LX>(S, ob.node_begin, ob.node_end, lr,
+                                                                                      t, face, limit, c, dc, k);
         else found = walk_bvh<ANY, STATS, (FEAT & FEAT_BIGLEAF) != 0>(S, ob.node_begin, ob.node_end, lr, t, face, limit, c);
         if (found) {
             h.t = t; h.obj = k; h.face = face; h.o = r.o;
@@ -1309,6 +1324,125 @@ DEV float slab_cons_v(float lx, float ly, float lz, float hx, float hy, float hz
     tnear = tmin;
     return __builtin_elementwise_minimum(
         vmin3(tmax + 1e-30f, (tmax - fmaf(tmin, 1.0f - 0x1p-20f, -1e-30f)) + 1e-30f, minTc - tmin), livef);
+}
+
+// The closest-hit packet walk, exact at leaves only (walk_bvh_packet<false, false, true>; DESIGN.md §2
+// "Leaf-exact walks").  Parent boxes are exact min/max unions of their children and box_hit is
+// monotone in the box and in minT, and a lane's minT never rises: in the reference's pre-order walk
+// a lane tests the faces of leaf L iff L's own box passes at the minT the lane holds when pre-order
+// reaches L (every ancestor was tested earlier, at a minT at least as large, and contains L's box).
+// So inner-node decisions change which boxes are looked at, never a hit or a tie, provided
+//   1. leaves come in pre-order and each leaf box gets the exact test (box_pass_v) per lane, and
+//   2. no inner test culls a box the exact test keeps (slab_cons_v's predicate: it only adds boxes).
+// The inner step is therefore the conservative value alone -- no certainty term, no exact fallback
+// for sure or unsure lanes -- and the lanes carry no resume / rel / act: a lane that would have
+// sat a subtree out fails its leaves there on its own.  The wave descends when any lane's value
+// is > 0.  Lanes that cannot use the conservative form (off the fast path, |o inv| not finite:
+// kc = NaN makes their value NaN; or a NaN from the box) take box_hit at inner nodes in a
+// wave-uniform branch: voting "pass" instead would drag the wave of an axis-aligned camera ray
+// through the whole tree.  A leaf takes the exact test alone.  (The conservative value first, as
+// the wave's ballot, so that a leaf nobody reaches costs no exact test: most leaves a coherent
+// wave visits are reached by some lane, and those then pay both tests -- k_frame 0.2540 -> 0.2459
+// ms that way against 0.2391 with the exact test alone, profiles/r12_leaf_walk_ab.txt.)
+DEV float slab_cons_pk(float lx, float ly, float lz, float hx, float hy, float hz, const SlabCons& s, float minTc) {
+    const float tx1 = fmaf(lx, s.ix, s.ax), tx2 = fmaf(hx, s.ix, s.bx);
+    const float ty1 = fmaf(ly, s.iy, s.ay), ty2 = fmaf(hy, s.iy, s.by);
+    const float tz1 = fmaf(lz, s.iz, s.az), tz2 = fmaf(hz, s.iz, s.bz);
+    const float tmin = fmaxf(fmaxf(fminf(tx1, tx2), fminf(ty1, ty2)), fminf(tz1, tz2));
+    const float tmax = fminf(fminf(fmaxf(tx1, tx2), fmaxf(ty1, ty2)), fmaxf(tz1, tz2));
+    return vmin3(tmax + 1e-30f, (tmax - fmaf(tmin, 1.0f - 0x1p-20f, -1e-30f)) + 1e-30f, minTc - tmin);
+}
+template <bool DEFER>
+DEV bool walk_bvh_packet_lx(const DevScene& S, int begin, int end, const Ray& r, float& minT, int& hitFace,
+                            DeferCtx* dc, int k) {
+    begin = __builtin_amdgcn_readfirstlane(begin);
+    end = __builtin_amdgcn_readfirstlane(end);
+    const int face0 = hitFace;
+    const RayRcp q = ray_rcp(r);
+    const SlabCons sc = slab_cons_ray(r, q);
+    // (the exact test's constants stay live beside the conservative ones: made at each leaf from a
+    // laundered origin, as walk_wide_any_pk's exact block does, the kernels' registers are the same
+    // and k_frame is slower, 0.2399 against 0.2359 ms, profiles/r12_leaf_walk_ab.txt)
+    const SlabFma sf = slab_fma(r, q);
+    const float slack0 = slab_slack0(sf, q.fast);
+    const float kc = (q.fast & sc.ok) ? 1.0f + 0x1p-20f : __builtin_nanf("");
+    float minTc = minT * kc;                         // follows minT: renewed after a leaf's faces
+    int i = begin;                                   // wave-uniform
+    while (i < end) {
+        i = __builtin_amdgcn_readfirstlane(i);
+        const int ip1 = i + 1;
+        rtg_s8 nd;
+        sload_node(rec_at<32>(S.nodes, i), nd);
+        const float4 a = f4(nd[0], nd[1], nd[2], nd[3]), b = f4(nd[4], nd[5], nd[6], nd[7]);
+        const int skip = nd[6], leaf = nd[7];
+        float pv;                                    // > 0: the lane passes
+        if (leaf < 0) {
+            pv = slab_cons_pk(a.x, a.y, a.z, a.w, b.x, b.y, sc, minTc);
+            if (__builtin_expect(__ballot(pv != pv) != 0, 0)) {
+                if (pv != pv) pv = box_hit(a.x, a.y, a.z, a.w, b.x, b.y, r, minT) ? 1.0f : -1.0f;
+            }
+        } else {
+            // the exact decision at the lane's own minT (slack0 = inf off the fast path: box_hit)
+            pv = box_pass_v(a.x, a.y, a.z, a.w, b.x, b.y, r, sf, minT, INFINITY, slack0);
+        }
+        bool pass = pv > 0.0f;
+        // (the next node and the leaf to test: walk_bvh_packet's five scalar instructions)
+        const int cur = i;
+        int lf;
+        {
+            const uint64_t pm = __builtin_amdgcn_ballot_w64(pass);
+            int nx;
+            asm("s_cmp_lg_u64 %[pm], 0\n\t"
+                "s_cselect_b32 %[lf], %[leaf], 0\n\t"
+                "s_cmp_lt_i32 %[lf], 0\n\t"
+                "s_cselect_b32 %[nx], %[ip1], %[skip]"
+                : [lf] "=&s"(lf), [nx] "=&s"(nx)
+                : [pm] "s"(pm), [leaf] "s"(leaf), [ip1] "s"(ip1), [skip] "s"(skip)
+                : "scc");
+            i = nx;
+        }
+        if (lf > 0) {
+            int first = leaf >> 8, cnt = leaf & 255;
+            if (leaf == LEAF_EXT) {
+                const int2 e = S.node_ext[cur];
+                first = __builtin_amdgcn_readfirstlane(e.x);
+                cnt = __builtin_amdgcn_readfirstlane(e.y);
+            }
+            if constexpr (DEFER) {
+                const uint64_t m = __ballot(pass);
+                if (cnt > kDeferLeaf && __popcll(m) <= RTG_DEFER_LANES) {
+                    // one atomic per wave for the lanes that reached the leaf
+                    const int lane = threadIdx.x & 63, lead = __ffsll((long long)m) - 1;
+                    int base = 0;
+                    if (lane == lead) base = atomicAdd(dc->count, __popcll(m));
+                    base = __shfl(base, lead);
+                    const int slot = base + __popcll(m & ((1ull << lane) - 1ull));
+                    if (pass && slot < dc->cap) {
+                        float4* qe = dc->e + 3 * (size_t)slot;
+                        qe[0] = make_float4(r.o.x, r.o.y, r.o.z, minT);
+                        qe[1] = make_float4(r.d.x, r.d.y, r.d.z, __int_as_float(dc->ray));
+                        qe[2] = make_float4(__int_as_float(first), __int_as_float(cnt), __int_as_float(k), 0.f);
+                        dc->deferred = true;
+                        pass = false;                // queued: no test here, minT unchanged
+                    }
+                    // (a lane whose entry did not fit tests the leaf below)
+                }
+            }
+            for (int f = first; f < first + cnt; ++f) {
+                rtg_s8 ra;
+                rtg_s4 rb;
+                sload_rec(rec_at<48>(S.tris, f), ra, rb);
+                const float4 R[3] = {f4(ra[0], ra[1], ra[2], ra[3]), f4(ra[4], ra[5], ra[6], ra[7]),
+                                     f4(rb[0], rb[1], rb[2], rb[3])};
+                float t;
+                const bool ok = tri_test_pk(R, r, minT, t, pass ? 1.0f : -1.0f) > 0.0f;
+                minT = ok ? t : minT;
+                hitFace = ok ? f : hitFace;
+            }
+            minTc = minT * kc;
+        }
+    }
+    return hitFace != face0;
 }
 
 template <bool STATS, bool DEFER = false>
