@@ -36,6 +36,8 @@
 //       Caller-supplied rays through the reference's own IntersectObjects / PerformShading
 //       (radiance_mode below); the radiance-ray goldens.  This translation unit alone is compiled
 //       with -fno-access-control (oracle/Makefile) so that it can call those private members.
+//   refdriver bvh <scene.xml> <out.bin>
+//       The BVH of every mesh as the reference's parser leaves it (bvh_mode below); the BVH goldens.
 #define STB_IMAGE_WRITE_IMPLEMENTATION
 #include "stb_image_write.h"
 #define STB_IMAGE_IMPLEMENTATION
@@ -417,7 +419,57 @@ static int radiance_mode(const char* xml, const char* in, const char* out, int c
     return 0;
 }
 
+// The BVH the reference's own parser builds (Mesh::ConstructBVH, mesh.cpp:23-156), as it stands
+// after loadFromXml.  out.bin: "RTGB" int32 number of meshes (every non-instance Shape of
+// scene.meshes, in list order), then per mesh int32 nodes, int32 faces; per node (allocation
+// order, the nextFreeNodeIdx nodes in use) 9 int32: the bits of bbox min.xyz and max.xyz, the
+// index of the left child in the bvh array (-1: none; the right child is the next one), firstFace,
+// faceCount; per face in final order 6 int32: the bits of center.xyz and v0_id, v1_id, v2_id.
+static int bvh_mode(const char* xml, const char* out) {
+    Scene scene;
+    scene.loadFromXml(xml);
+    std::vector<int32_t> res;
+    int32_t nmesh = 0;
+    for (size_t k = 0; k < scene.meshes.size(); k++) {
+        if (scene.meshes[k]->isInstance) continue;
+        Mesh* m = static_cast<Mesh*>(scene.meshes[k]);
+        ++nmesh;
+        const int32_t nn = (int32_t)m->nextFreeNodeIdx, nf = (int32_t)m->faces.size();
+        res.push_back(nn);
+        res.push_back(nf);
+        for (int32_t i = 0; i < nn; ++i) {
+            const BVH& b = m->bvh[i];
+            const float box[6] = {b.bbox.minCorner.x, b.bbox.minCorner.y, b.bbox.minCorner.z,
+                                  b.bbox.maxCorner.x, b.bbox.maxCorner.y, b.bbox.maxCorner.z};
+            int32_t bits[6];
+            std::memcpy(bits, box, 24);
+            res.insert(res.end(), bits, bits + 6);
+            res.push_back(b.left ? (int32_t)(b.left - &m->bvh[0]) : -1);
+            res.push_back((int32_t)b.firstFace);
+            res.push_back((int32_t)b.faceCount);
+        }
+        for (int32_t i = 0; i < nf; ++i) {
+            const Face& f = m->faces[i];
+            const float c[3] = {f.center.x, f.center.y, f.center.z};
+            int32_t bits[3];
+            std::memcpy(bits, c, 12);
+            res.insert(res.end(), bits, bits + 3);
+            res.push_back(f.v0_id);
+            res.push_back(f.v1_id);
+            res.push_back(f.v2_id);
+        }
+    }
+    FILE* f = std::fopen(out, "wb");
+    if (!f) { std::perror(out); return 1; }
+    std::fwrite("RTGB", 1, 4, f);
+    std::fwrite(&nmesh, 4, 1, f);
+    std::fwrite(res.data(), 4, res.size(), f);
+    std::fclose(f);
+    return 0;
+}
+
 int main(int argc, char** argv) {
+    if (argc >= 4 && !std::strcmp(argv[1], "bvh")) return bvh_mode(argv[2], argv[3]);
     if (argc >= 5 && !std::strcmp(argv[1], "radiance"))
         return radiance_mode(argv[2], argv[3], argv[4], argc > 5 ? std::atoi(argv[5]) : 0);
     if (argc >= 5 && !std::strcmp(argv[1], "rays")) return rays_mode(argv[2], argv[3], argv[4]);

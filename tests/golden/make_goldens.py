@@ -14,6 +14,7 @@ Fixture scenes live in tests/golden/scenes/: copies of the reference's own scene
                                                    # and scenes/edge_lattice.xml
     python tests/golden/make_goldens.py radiance_rays   # only the radiance-ray goldens
                                                         # (radiance_rays_<scene>.npz)
+    python tests/golden/make_goldens.py bvh        # only the BVH goldens (bvh_<case>.npz, bvh_manifest.json)
 """
 import hashlib
 import json
@@ -1055,11 +1056,84 @@ def make_radiance_rays(names):
         print("radiance rays", name, int(keep.sum()), "dropped per class", dropped.tolist(), "bytes", size)
 
 
+# BVH goldens (bvh_<case>.npz): the BVH the reference's own parser builds (refdriver bvh) for the
+# adversarial meshes of tests/bvh_cases.py.  Per mesh k: nodes<k> (n, 9) int32 -- box bits, left
+# child, firstFace, faceCount in allocation order -- and faces<k> (n, 6) int32 -- centre bits and
+# the three vertex ids, in final order; sha256: of the generated vertex and index bits
+# (Case.vertex_sha256), so that a drifting generator fails loudly.  bvh_manifest.json lists the
+# cases, their vertex hashes and the cases dropped (the reference crashed, or two runs differed).
+BVH_MAX_BYTES = 256 * 1024
+
+
+def run_ref_bvh(xml, cwd):
+    """refdriver bvh: [(nodes (n, 9), faces (n, 6)) int32 per mesh], or None if it does not return."""
+    dst = os.path.join(cwd, "_bvh_out.bin")
+    try:
+        rc = subprocess.run([DRIVER, "bvh", xml, dst], cwd=cwd, stdout=subprocess.DEVNULL, timeout=600).returncode
+        if rc != 0:
+            return None
+        raw = np.frombuffer(open(dst, "rb").read(), np.int32)
+    except subprocess.TimeoutExpired:
+        return None
+    finally:
+        if os.path.exists(dst):
+            os.remove(dst)
+    assert raw[0] == np.frombuffer(b"RTGB", np.int32)[0]
+    out, at = [], 2
+    for _ in range(raw[1]):
+        nn, nf = int(raw[at]), int(raw[at + 1])
+        at += 2
+        nodes = raw[at:at + 9 * nn].reshape(nn, 9).copy()
+        at += 9 * nn
+        faces = raw[at:at + 6 * nf].reshape(nf, 6).copy()
+        at += 6 * nf
+        out.append((nodes, faces))
+    assert at == raw.size
+    return out
+
+
+def make_bvh(names=None):
+    import tempfile
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import bvh_cases
+    path = os.path.join(HERE, "bvh_manifest.json")
+    man = json.load(open(path)) if names and os.path.exists(path) else {"cases": {}, "dropped": {}}
+    for name in names or bvh_cases.NAMES:
+        case = bvh_cases.get(name)
+        man["cases"].pop(name, None)
+        man["dropped"].pop(name, None)
+        with tempfile.TemporaryDirectory() as d:
+            bvh_cases.write_scene(case, d, name)
+            a, b = run_ref_bvh(name + ".xml", d), run_ref_bvh(name + ".xml", d)
+        if a is None or b is None:
+            man["dropped"][name] = "the reference does not return"
+        elif len(a) != len(b) or not all(np.array_equal(x, y) for p, q in zip(a, b) for x, y in zip(p, q)):
+            man["dropped"][name] = "two runs of the reference differ"
+        if name in man["dropped"]:
+            print("bvh", name, "dropped:", man["dropped"][name])
+            continue
+        assert len(a) == len(case.meshes)
+        arrays = {"sha256": np.array(case.vertex_sha256())}
+        for k, (nodes, faces) in enumerate(a):
+            arrays[f"nodes{k}"], arrays[f"faces{k}"] = nodes, faces
+        out = os.path.join(HERE, f"bvh_{name}.npz")
+        np.savez_compressed(out, **arrays)
+        size = os.path.getsize(out)
+        assert size <= BVH_MAX_BYTES, (name, size)
+        man["cases"][name] = {"sha256": case.vertex_sha256(), "meshes": len(a), "bytes": size}
+        print("bvh", name, [(len(n), len(f)) for n, f in a], "bytes", size)
+    with open(path, "w") as f:
+        json.dump(man, f, indent=1, sort_keys=True)
+
+
 def main():
     if not os.path.exists(DRIVER):
         sys.exit(f"{DRIVER} missing: build it with `make -C {os.path.join(ROOT, 'oracle')}` (needs /root/reference)")
     man = {}
     only = set(sys.argv[1:])
+    if only and all(o == "bvh" or o.startswith("bvh_") for o in only):
+        make_bvh(None if "bvh" in only else [o[len("bvh_"):] for o in sorted(only)])
+        return
     if only and only <= {"radiance_rays"} | {"radiance_rays_" + n for n in RADIANCE_SCENES}:
         make_radiance_rays(RADIANCE_SCENES if "radiance_rays" in only else [o[len("radiance_rays_"):] for o in sorted(only)])
         return
@@ -1106,6 +1180,7 @@ def main():
     if not only:
         make_edge_rays(EDGE_SCENES)
         make_radiance_rays(RADIANCE_SCENES)
+        make_bvh()
 
 
 if __name__ == "__main__":
