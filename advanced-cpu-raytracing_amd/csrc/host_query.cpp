@@ -10,6 +10,9 @@
 //   Sphere::Intersect                  sphere.cpp:13-70
 //   InstancedMesh::Intersect           instancedMesh.cpp:16-66
 //   BoundingBox::doesIntersectWith     shape.hpp:78-100
+//
+// rtg_desc_trace_rays_multi: the same walk with the ray keeping its k smallest accepted distances
+// (multi_one below) -- the same box_hit / face_hit and sphere arithmetic, minT the k-th distance.
 #include "host_query.hpp"
 
 #include <algorithm>
@@ -213,7 +216,164 @@ void trace_one(const rtg_scene_desc* d, const rtg_ray& q, bool any, rtg_hit& out
     normal[0] = n.x; normal[1] = n.y; normal[2] = n.z;
 }
 
+// ---- multi-hit: the same walk keeping the k smallest accepted distances (rtg_desc_trace_rays_multi)
+
+// The held hits in ascending t.  minT is the k-th distance, or tmax while fewer are held.
+struct HitList {
+    int k;
+    float tmax;
+    int n = 0;
+    float t[RTG_MULTIHIT_MAX];
+    int obj[RTG_MULTIHIT_MAX], face[RTG_MULTIHIT_MAX];
+    float minT() const { return n < k ? tmax : t[k - 1]; }
+    // an accepted hit (tn < minT): after every held hit of equal t; the last falls off a full list
+    void insert(float tn, int o, int f) {
+        int j = n < k ? n++ : k - 1;
+        for (; j > 0 && tn < t[j - 1]; --j) {
+            t[j] = t[j - 1]; obj[j] = obj[j - 1]; face[j] = face[j - 1];
+        }
+        t[j] = tn; obj[j] = o; face[j] = f;
+    }
+};
+
+// Sphere::Intersect with both roots: sphere_hit's arithmetic and selection; `sel` is the root the
+// reference reports, `other` the one it leaves.  False: no real root.
+bool sphere_roots(const rtg_object& ob, const HRay& lr, float& sel, float& other) {
+    const V3 center = from_f3(ob.center);
+    V3 oc = lr.o - center;
+    float c = dot(oc, oc) - (ob.radius * ob.radius);
+    float b = 2 * dot(lr.d, oc);
+    float a = dot(lr.d, lr.d);
+    float delta = b * b - (4 * a * c);
+    if (delta < 0.0f) return false;
+    delta = sqrtf(delta);
+    a = (float)(2.0 * a);
+    float t1 = (-b + delta) / a;
+    float t2 = (-b - delta) / a;
+    sel = t2; other = t1;                                          // t1 == t2, or unordered
+    if (t1 < t2) { if (t1 > 0.0f) { sel = t1; other = t2; } }      // else t2, as above
+    else if (t2 < t1) { if (!(t2 > 0.0f)) { sel = t1; other = t2; } }
+    return true;
+}
+
+struct MultiWalk {
+    const rtg_bvh_node* nodes;
+    const rtg_face* faces;
+    HRay r;                       // local ray
+    HitList* L;
+    int obj, face_offset;
+};
+
+// BVH::IntersectBVH, every accepted face into the list
+void intersect_bvh_multi(MultiWalk& w, int k) {
+    const rtg_bvh_node& n = w.nodes[k];
+    if (!box_hit(n.bmin, n.bmax, w.r, w.L->minT())) return;
+    if (n.left < 0) {
+        for (int i = n.first; i < n.first + n.count; ++i) {
+            float t;
+            if (face_hit(w.faces[i], w.r, w.L->minT(), t)) w.L->insert(t, w.obj, w.face_offset + i);
+        }
+    } else {
+        intersect_bvh_multi(w, n.left);
+        intersect_bvh_multi(w, n.left + 1);
+    }
+}
+
+// trace_one's object loop (closest hit) on a list
+void multi_one(const rtg_scene_desc* d, const rtg_ray& q, int kk, rtg_hit* out, int32_t* count) {
+    HRay r;
+    r.o = V3(q.ox, q.oy, q.oz);
+    r.d = V3(q.dx, q.dy, q.dz);
+    const float time = q.time;
+    HitList L;
+    L.k = kk;
+    L.tmax = q.tmax;
+    for (int k = 0; k < d->num_objects; ++k) {
+        const rtg_object& ob = d->objects[k];
+        if (ob.kind == RTG_OBJ_SPHERE) {
+            float t, u;
+            if (sphere_roots(ob, local_ray(ob, r, time), t, u)) {
+                if (t < L.minT() && t > 0.0f) L.insert(t, k, -1);
+                if (u != t && u < L.minT() && u > 0.0f) L.insert(u, k, -2);
+            }
+            continue;
+        }
+        const rtg_mesh& M = d->meshes[ob.mesh];
+        if (ob.kind == RTG_OBJ_INSTANCE) {
+            HRay wr = r;
+            if (ob.flags & RTG_OBJF_MOTION_BLUR) wr.o = wr.o + from_f3(ob.motion_blur) * time;
+            if (!box_hit(ob.bbox_min, ob.bbox_max, wr, L.minT())) {
+                r.o = wr.o;
+                continue;
+            }
+        }
+        MultiWalk w;
+        w.nodes = d->nodes + M.node_offset;
+        w.faces = d->faces + M.face_offset;
+        w.r = local_ray(ob, r, time);
+        w.L = &L;
+        w.obj = k;
+        w.face_offset = M.face_offset;
+        if (ob.kind == RTG_OBJ_MESH && !box_hit(ob.bbox_min, ob.bbox_max, w.r, L.minT())) continue;
+        if (M.node_count <= 0) continue;
+        intersect_bvh_multi(w, 0);
+    }
+    for (int j = 0; j < kk; ++j) {
+        const bool filled = j < L.n;
+        out[j].t = filled ? L.t[j] : q.tmax;
+        out[j].object = filled ? L.obj[j] : -1;
+        out[j].face = filled ? L.face[j] : -1;
+        out[j].pad = 0;
+    }
+    if (count) *count = L.n;
+}
+
+// fn(begin, end) over [0, n) in contiguous chunks on a few threads: rays are independent
+template <typename Fn>
+void chunked(int64_t n, Fn&& work) {
+    const int64_t kChunk = 4096;
+    const int nt = (int)std::min<int64_t>(std::min(8u, std::max(1u, std::thread::hardware_concurrency())),
+                                          (n + kChunk - 1) / kChunk);
+    if (nt <= 1) {
+        work(0, n);
+        return;
+    }
+    std::vector<std::thread> pool;
+    const int64_t per = (n + nt - 1) / nt;
+    for (int t = 0; t < nt; ++t) {
+        const int64_t b = t * per, e = std::min(n, b + per);
+        if (b < e) pool.emplace_back(work, b, e);
+    }
+    for (auto& th : pool) th.join();
+}
+
+const char* check_desc(const rtg_scene_desc* d) {
+    if (d->num_faces > 0 && d->num_nodes == 0)
+        return "the description has no BVH nodes (RTG_LOAD_DEVICE_BVH): it is for rtg_scene_create only";
+    for (int i = 0; i < d->num_objects; ++i) {
+        const rtg_object& o = d->objects[i];
+        if (o.kind != RTG_OBJ_SPHERE && (o.mesh < 0 || o.mesh >= d->num_meshes)) return "object with a bad mesh index";
+    }
+    return nullptr;
+}
+
 }  // namespace
+
+int host_trace_rays_multi(const rtg_scene_desc* d, const rtg_ray* rays, int64_t n, int32_t k, uint32_t flags,
+                          rtg_hit* hits, int32_t* counts, std::string& err) {
+    if (!d) { err = "null description"; return RTG_ERR_INVALID; }
+    if (n < 0 || n > INT32_MAX) { err = "ray count out of range"; return RTG_ERR_INVALID; }
+    if (k < 1 || k > RTG_MULTIHIT_MAX) { err = "k out of range [1, RTG_MULTIHIT_MAX]"; return RTG_ERR_INVALID; }
+    if (flags & RTG_QUERY_ANY_HIT) { err = "RTG_QUERY_ANY_HIT does not apply to a multi-hit query"; return RTG_ERR_INVALID; }
+    if (flags & ~(uint32_t)RTG_QUERY_COHERENT) { err = "unknown query flags"; return RTG_ERR_INVALID; }
+    if (const char* e = check_desc(d)) { err = e; return RTG_ERR_INVALID; }
+    if (n == 0) return RTG_OK;
+    if (!rays || !hits) { err = "null buffer"; return RTG_ERR_INVALID; }
+    chunked(n, [&](int64_t b, int64_t e) {
+        for (int64_t i = b; i < e; ++i) multi_one(d, rays[i], k, hits + i * k, counts ? counts + i : nullptr);
+    });
+    return RTG_OK;
+}
 
 int host_trace_rays(const rtg_scene_desc* d, const rtg_ray* rays, int64_t n, uint32_t flags, rtg_hit* hits,
                     float* normals, std::string& err) {
@@ -234,24 +394,9 @@ int host_trace_rays(const rtg_scene_desc* d, const rtg_ray* rays, int64_t n, uin
         }
     }
     const bool any = (flags & RTG_QUERY_ANY_HIT) != 0;
-    // rays are independent: contiguous chunks over a few threads
-    const int64_t kChunk = 4096;
-    const int nt = (int)std::min<int64_t>(std::min(8u, std::max(1u, std::thread::hardware_concurrency())),
-                                          (n + kChunk - 1) / kChunk);
-    auto work = [&](int64_t b, int64_t e) {
+    chunked(n, [&](int64_t b, int64_t e) {
         for (int64_t i = b; i < e; ++i) trace_one(d, rays[i], any, hits[i], normals ? normals + 4 * i : nullptr);
-    };
-    if (nt <= 1) {
-        work(0, n);
-        return RTG_OK;
-    }
-    std::vector<std::thread> pool;
-    const int64_t per = (n + nt - 1) / nt;
-    for (int t = 0; t < nt; ++t) {
-        const int64_t b = t * per, e = std::min(n, b + per);
-        if (b < e) pool.emplace_back(work, b, e);
-    }
-    for (auto& th : pool) th.join();
+    });
     return RTG_OK;
 }
 

@@ -14,4 +14,9 @@ namespace rtg {
 int host_trace_rays(const rtg_scene_desc* d, const rtg_ray* rays, int64_t n, uint32_t flags, rtg_hit* hits,
                     float* normals, std::string& err);
 
+// The same walk keeping the k nearest hits per ray (rtgpu.h rtg_desc_trace_rays_multi): hits n * k,
+// ray-major; counts nullable.
+int host_trace_rays_multi(const rtg_scene_desc* d, const rtg_ray* rays, int64_t n, int32_t k, uint32_t flags,
+                          rtg_hit* hits, int32_t* counts, std::string& err);
+
 }  // namespace rtg

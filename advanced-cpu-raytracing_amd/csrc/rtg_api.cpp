@@ -81,7 +81,7 @@ struct SceneGeom {
 };
 
 // The host-buffer queries' scratch (rtg_scene::q): one slot per kind of buffer
-enum QuerySlot { Q_RAYS, Q_HITS, Q_NORMALS, Q_RADIANCE, Q_PIXEL_IDS, Q_SURFACE, Q_SLOTS };
+enum QuerySlot { Q_RAYS, Q_HITS, Q_NORMALS, Q_RADIANCE, Q_PIXEL_IDS, Q_SURFACE, Q_COUNTS, Q_SLOTS };
 
 struct rtg_scene {
     int device = 0;
@@ -1181,6 +1181,42 @@ int rtg_trace_rays(rtg_scene* s, const rtg_ray* rays, int64_t n, uint32_t flags,
     return unstage(s, bufs);
 }
 
+// ---- multi-hit queries (rtg_multihit.hip)
+static int multi_args(const rtg_scene* s, const void* rays, int64_t n, int32_t k, uint32_t flags, const void* hits) {
+    if (!s) return set_err(RTG_ERR_INVALID, "null scene");
+    if (n < 0 || n > INT32_MAX) return set_err(RTG_ERR_INVALID, "%lld rays: at most INT32_MAX per call", (long long)n);
+    if (k < 1 || k > RTG_MULTIHIT_MAX)
+        return set_err(RTG_ERR_INVALID, "k = %d: a multi-hit query holds 1 to %d hits per ray", k, RTG_MULTIHIT_MAX);
+    if (flags & RTG_QUERY_ANY_HIT) return set_err(RTG_ERR_INVALID, "RTG_QUERY_ANY_HIT does not apply to a multi-hit query");
+    if (flags & ~(uint32_t)RTG_QUERY_COHERENT) return set_err(RTG_ERR_INVALID, "unknown query flags 0x%x", flags);
+    if (n > 0 && (!rays || !hits)) return set_err(RTG_ERR_INVALID, "null buffer");
+    return RTG_OK;
+}
+
+int rtg_trace_rays_multi_device(rtg_scene* s, const rtg_ray* d_rays, int64_t n, int32_t k, uint32_t flags,
+                                rtg_hit* d_hits, int32_t* d_counts, void* stream) {
+    int rc = multi_args(s, d_rays, n, k, flags, d_hits);
+    if (rc || n == 0) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(rtg::launch_multihit(s->ds, s->feat, d_rays, (int)n, k, d_hits, d_counts, (hipStream_t)stream));
+    return RTG_OK;
+}
+
+int rtg_trace_rays_multi(rtg_scene* s, const rtg_ray* rays, int64_t n, int32_t k, uint32_t flags, rtg_hit* hits,
+                         int32_t* counts) {
+    int rc = multi_args(s, rays, n, k, flags, hits);
+    if (rc || n == 0) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t N = (size_t)n;
+    const std::initializer_list<Staged> bufs = {{Q_RAYS, N * sizeof(rtg_ray), rays, nullptr},
+                           {Q_HITS, N * (size_t)k * sizeof(rtg_hit), nullptr, hits},
+                           {Q_COUNTS, counts ? N * sizeof(int32_t) : 0, nullptr, counts}};
+    if ((rc = stage(s, bufs))) return rc;
+    HIP_TRY(rtg::launch_multihit(s->ds, s->feat, (rtg_ray*)s->q[Q_RAYS].p, (int)n, k, (rtg_hit*)s->q[Q_HITS].p,
+                                 counts ? (int*)s->q[Q_COUNTS].p : nullptr, s->stream));
+    return unstage(s, bufs);
+}
+
 // the camera record and row range of a camera-ray batch
 static int camera_rays_args(const rtg_scene* s, const rtg_render_opts* o, const void* rays, rtg::DevCamera& C,
                             int& row_begin, int& row_end) {
@@ -1318,6 +1354,18 @@ int rtg_desc_trace_rays(const rtg_scene_desc* d, const rtg_ray* rays, int64_t n,
         rc = rtg::host_trace_rays(d, rays, n, flags, hits, normals, err);
     } catch (const std::exception& e) {
         return set_err(RTG_ERR_NOMEM, "rtg_desc_trace_rays: %s", e.what());
+    }
+    return rc == RTG_OK ? RTG_OK : set_err(rc, "%s", err.c_str());
+}
+
+int rtg_desc_trace_rays_multi(const rtg_scene_desc* d, const rtg_ray* rays, int64_t n, int32_t k, uint32_t flags,
+                              rtg_hit* hits, int32_t* counts) {
+    std::string err;
+    int rc;
+    try {
+        rc = rtg::host_trace_rays_multi(d, rays, n, k, flags, hits, counts, err);
+    } catch (const std::exception& e) {
+        return set_err(RTG_ERR_NOMEM, "rtg_desc_trace_rays_multi: %s", e.what());
     }
     return rc == RTG_OK ? RTG_OK : set_err(rc, "%s", err.c_str());
 }

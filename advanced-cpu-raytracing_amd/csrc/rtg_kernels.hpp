@@ -69,6 +69,10 @@ hipError_t launch_query(const DevScene& S, int feat, const rtg_ray* rays, int n,
                         float4* normals, hipStream_t stream);
 hipError_t launch_camera_rays(const DevCamera& C, int row_begin, int row_end, int sample, unsigned long long seed,
                               rtg_ray* rays, hipStream_t stream);
+// multi-hit queries (rtg_multihit.hip): the k nearest hits of n rays (k in [1, RTG_MULTIHIT_MAX]), one
+// ray per lane; hits: n * k records, ray-major; counts nullable (filled slots per ray).
+hipError_t launch_multihit(const DevScene& S, int feat, const rtg_ray* rays, int n, int k, rtg_hit* hits, int* counts,
+                           hipStream_t stream);
 // surface queries (rtg_surface.hip): closest hit of n rays, one ray per lane, with the hit's shading
 // normal (normal / bump maps applied), texture coordinates, geometric normal, material and
 // GetDiffuse's coefficient; flags: RTG_QUERY_COHERENT only.  sk / feat as for launch_mega (a scene

@@ -139,4 +139,8 @@ auto with_step_variant(int sk, int feat, Fn&& fn) {
 // k_tree_shade: scenes with plain shading (textures and maps at most) take the lean variant
 constexpr int tree_shade_sk(int sk) { return (sk & ~SK_TEX) == 0 ? SK_TEX : SK_ALL; }
 
+// k_multihit: the hit list's slots per field (registers), k in [1, RTG_MULTIHIT_MAX] rounded up
+// to 2, 4 or 8
+constexpr int multi_kmax(int k) { return k <= 2 ? 2 : k <= 4 ? 4 : 8; }
+
 }  // namespace rtg

@@ -35,6 +35,7 @@ RTG_RENDER_SAMPLE_PASSES = 128
 RTG_LOAD_DEVICE_BVH = 1
 RTG_QUERY_ANY_HIT = 1
 RTG_QUERY_COHERENT = 2
+RTG_MULTIHIT_MAX = 8
 RTG_RADIANCE_CAMERA_EYE = 1
 # rtg_ray (32 B) and rtg_hit (16 B) as NumPy structured dtypes
 RAY_DTYPE = np.dtype([("ox", "<f4"), ("oy", "<f4"), ("oz", "<f4"), ("tmax", "<f4"),
@@ -176,6 +177,7 @@ EXPORTED = [
     "rtg_scene_create_multi", "rtg_scene_num_devices", "rtg_part_runs", "rtg_copy_part_to_host",
     "rtg_host_alloc", "rtg_host_free", "rtg_host_register", "rtg_host_unregister",
     "rtg_trace_rays_device", "rtg_trace_rays", "rtg_camera_rays_device", "rtg_camera_rays", "rtg_desc_trace_rays",
+    "rtg_trace_rays_multi_device", "rtg_trace_rays_multi", "rtg_desc_trace_rays_multi",
     "rtg_radiance_rays_device", "rtg_radiance_rays",
     "rtg_surface_rays_device", "rtg_surface_rays",
     "rtg_scene_update", "rtg_scene_set_camera", "rtg_scene_num_cameras", "rtg_camera_setup",
@@ -243,7 +245,10 @@ def lib() -> ctypes.CDLL:
     L.rtg_camera_rays_device.argtypes = [vp, P(RenderOpts), vp, vp]
     L.rtg_camera_rays.argtypes = [vp, P(RenderOpts), vp]
     L.rtg_desc_trace_rays.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_uint32, vp, vp]
-    L.rtg_radiance_rays_device.argtypes = [vp, P(RadianceOpts), vp, vp, ctypes.c_int64, vp, vp]
+    L.rtg_trace_rays_multi_device.argtypes = [vp, vp, ctypes.c_int64, i32, ctypes.c_uint32, vp, vp, vp]
+    L.rtg_trace_rays_multi.argtypes = [vp, vp, ctypes.c_int64, i32, ctypes.c_uint32, vp, vp]
+    L.rtg_desc_trace_rays_multi.argtypes = [vp, vp, ctypes.c_int64, i32, ctypes.c_uint32, vp, vp]
+    L.rtg_radiance_rays_device.argtypes =[vp, P(RadianceOpts), vp, vp, ctypes.c_int64, vp, vp]
     L.rtg_radiance_rays.argtypes = [vp, P(RadianceOpts), vp, vp, ctypes.c_int64, vp]
     L.rtg_surface_rays_device.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_uint32, vp, vp]
     L.rtg_surface_rays.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_uint32, vp]
@@ -287,6 +292,18 @@ def _query(fn, handle, rays, any_hit, coherent, normals):
     _check(fn(handle, rays.ctypes.data, n, _query_flags(any_hit, coherent), hits.ctypes.data,
               nrm.ctypes.data if normals else None))
     return (hits, nrm) if normals else hits
+
+
+def _query_multi(fn, handle, rays, k, coherent, counts):
+    """Shared body of HostScene.trace_multi / DeviceScene.trace_multi: (n, k) hits, or (hits, counts)."""
+    rays = np.ascontiguousarray(rays, RAY_DTYPE)
+    n = rays.size
+    k = int(k)
+    hits = np.zeros((n, max(k, 0)), HIT_DTYPE)
+    cnt = np.zeros(n, np.int32) if counts else None
+    _check(fn(handle, rays.ctypes.data, n, k, _query_flags(False, coherent), hits.ctypes.data,
+              cnt.ctypes.data if counts else None))
+    return (hits, cnt) if counts else hits
 
 
 def device_count() -> int:
@@ -349,6 +366,12 @@ class HostScene:
         restated plainly -- the yardstick of DeviceScene.trace).  rays: RAY_DTYPE array.  Returns
         the HIT_DTYPE array, or (hits, normals (n, 4) float32) with ``normals=True``."""
         return _query(lib().rtg_desc_trace_rays, self.desc, rays, any_hit, coherent, normals)
+
+    def trace_multi(self, rays, k: int, coherent: bool = False, counts: bool = False):
+        """The k nearest hits along each ray on the host, no device (rtg_desc_trace_rays_multi: the
+        yardstick of DeviceScene.trace_multi).  Returns the (n, k) HIT_DTYPE array, or
+        (hits, counts (n,) int32) with ``counts=True``."""
+        return _query_multi(lib().rtg_desc_trace_rays_multi, self.desc, rays, k, coherent, counts)
 
     def num_cameras(self) -> int:
         n = 0
@@ -486,6 +509,20 @@ class DeviceScene:
         rays, n x 16 B hits, optionally n x 4 float32 normals) on ``stream``; flags RTG_QUERY_*."""
         _check(lib().rtg_trace_rays_device(self._s, rays_ptr or None, n, flags, hits_ptr or None,
                                            normals_ptr or None, stream or None))
+
+    def trace_multi(self, rays, k: int, coherent: bool = False, counts: bool = False):
+        """The k nearest hits along each ray, in order, on host arrays (rtg_trace_rays_multi;
+        synchronous): an (n, k) HIT_DTYPE array -- filled slots first in ascending t, unfilled ones
+        the miss record -- or (hits, counts (n,) int32) with ``counts=True``.  A sphere gives both
+        of its roots (face -1, then -2).  k in [1, RTG_MULTIHIT_MAX]; k = 1 is trace()."""
+        return _query_multi(lib().rtg_trace_rays_multi, self._s, rays, k, coherent, counts)
+
+    def trace_multi_device(self, rays_ptr: int, n: int, k: int, hits_ptr: int, counts_ptr: int = 0, stream: int = 0,
+                           flags: int = 0):
+        """Asynchronous multi-hit queries on device buffers (n x 32 B rays, n x k x 16 B hits
+        ray-major, optionally n int32 counts) on ``stream``; flags RTG_QUERY_COHERENT or 0."""
+        _check(lib().rtg_trace_rays_multi_device(self._s, rays_ptr or None, n, k, flags, hits_ptr or None,
+                                                 counts_ptr or None, stream or None))
 
     def camera_rays(self, camera: int = 0, rows=(0, 0), sample: int = 0, seed: int = 0x5EED) -> np.ndarray:
         """The rays render() traces for ``camera`` at sample index ``sample`` and ``seed``, rows

@@ -484,6 +484,53 @@ int rtg_desc_trace_rays(const rtg_scene_desc* desc, const rtg_ray* rays, int64_t
                         rtg_hit* hits, float* normals);
 
 /* ------------------------------------------------------------------------- */
+/* Multi-hit ray queries: the k nearest hits along a ray, in order.  Added    */
+/* symbols only -- RTG_ABI_VERSION stays 6.                                   */
+/* ------------------------------------------------------------------------- */
+#define RTG_MULTIHIT_MAX 8
+
+/* Semantics (IntersectObjects, raytracer.cpp:625-643, keeping k distances instead of one):
+ *  - The walk: the ray holds the k smallest accepted distances.  Its minT is the k-th of them, or
+ *    tmax while fewer than k are held, and it is used wherever the reference uses minT: box
+ *    tests, instance world boxes and group boxes, the moved-origin rule of a missed
+ *    motion-blurred instance, and t > 0 && t < minT at faces and spheres.  It never increases.
+ *    The boxes, the faces and their order are those of the closest-hit walk.
+ *  - Ordering and ties: an accepted hit enters the list in ascending t, after any held hit of
+ *    equal t; what falls off the end is dropped.  So among equal distances the first object
+ *    takes the earlier slot, and within a mesh the first face its BVH walk meets.
+ *  - Output: slot j of ray i is hits[i * k + j].  Filled slots come first and carry t, object,
+ *    face and pad = 0 as rtg_trace_rays does; unfilled slots are its miss record (tmax's own
+ *    bits, object = face = -1).  counts[i] (nullable) is the number of filled slots.  With k = 1
+ *    the result equals rtg_trace_rays without flags byte for byte, tmax <= 0 and NaN included.
+ *    (The answer for k is the first k slots of the answer for a larger k except on near ties: a
+ *    larger minT culls fewer boxes, and a face whose distance rounds a hair below the entry
+ *    distance of a box the shorter list's walk culls is found only by the longer one's.)
+ *  - Spheres contribute both roots: first the one Sphere::Intersect selects (sphere.cpp:13-70),
+ *    with face = -1, then the other one if it differs, under the same t > 0 && t < minT, with
+ *    face = -2.  (For k = 1 the second root can never displace the first.)
+ *  - RTG_OBJF_SHADOW_SKIP objects are hit like any other; time is the motion-blur time.
+ *  - flags: RTG_QUERY_COHERENT is accepted as a hint that never changes an answer (ignored
+ *    today); RTG_QUERY_ANY_HIT or an unknown bit is RTG_ERR_INVALID.  k outside
+ *    [1, RTG_MULTIHIT_MAX], n above INT32_MAX, or a null scene, ray or hit buffer is
+ *    RTG_ERR_INVALID; n == 0 is RTG_OK.
+ *  - Cost: an unbounded ray visits every box it pierces until k hits are held, and only then
+ *    culls at the k-th distance.  Give tmax where the caller knows a bound. */
+
+/* Device-resident buffers on `stream` (d_hits: n * k records; d_counts: n, nullable);
+ * asynchronous, allocates nothing and touches no render state.  A multi-device scene answers on
+ * its first replica.  Works on clones and after rtg_scene_update. */
+int rtg_trace_rays_multi_device(rtg_scene* scene, const rtg_ray* d_rays, int64_t n, int32_t k, uint32_t flags,
+                                rtg_hit* d_hits, int32_t* d_counts, void* stream);
+/* Same on host buffers (synchronous). */
+int rtg_trace_rays_multi(rtg_scene* scene, const rtg_ray* rays, int64_t n, int32_t k, uint32_t flags,
+                         rtg_hit* hits, int32_t* counts);
+/* Host only, no device: the same walk restated plainly over the description's own nodes -- the
+ * yardstick of the device query, bit for bit.  RTG_ERR_INVALID for a description without nodes
+ * (RTG_LOAD_DEVICE_BVH). */
+int rtg_desc_trace_rays_multi(const rtg_scene_desc* desc, const rtg_ray* rays, int64_t n, int32_t k, uint32_t flags,
+                              rtg_hit* hits, int32_t* counts);
+
+/* ------------------------------------------------------------------------- */
 /* Surface queries: what the renderer knows about the point a ray hits --     */
 /* shading normal, texture coordinates, material and diffuse coefficient.     */
 /* Added symbols and one type only -- RTG_ABI_VERSION stays 6.                */

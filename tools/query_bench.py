@@ -13,7 +13,7 @@ renders: RTG_FRAME_KERNEL=0 splits the sample pass into k_primary + k_shade_shad
 RTG_RENDER_EXACT_SHADOW gives k_shadow with the reference walk).  k_primary is the yardstick of
 (a): the same walk on the same rays, with a 32-byte ray read in place of ray generation.
 
-    python tools/query_bench.py [--launches 50] [--reps 3] [--out FILE] [--sections query,radiance,surface,update]
+    python tools/query_bench.py [--launches 50] [--reps 3] [--out FILE] [--sections query,radiance,surface,update,multi]
 
 The radiance section (rtg_radiance_rays_device, DeviceScene.radiance_device) runs on the same
 height field and on the path-tracing fixture tests/golden/scenes/pt_cornell.xml at its own size:
@@ -40,6 +40,11 @@ height field and on a C4-style instanced scene (scenes.config_c4 at one sample),
 of the same geometry (light moved; C4: a rotation and a translation of the instances changed): the
 wall-clock time of create, update, clone and clone + update as the median of --setups calls, and the
 render time of the updated scene against a freshly created one, interleaved.
+
+The multi section (rtg_trace_rays_multi_device, DeviceScene.trace_multi_device) runs on the same
+height field: the k nearest hits for k = 1, 2, 4, 8 on the camera's rays in pixel order and on the
+same rays randomly permuted, with trace_device (closest hit, no hint) on the same rays in the same
+session beside them.
 """
 import argparse
 import os
@@ -360,6 +365,81 @@ def update_main(args):
     return lines
 
 
+def multi_main(args):
+    """Multi-hit queries (rtg_trace_rays_multi_device) on the headline height field: lines of text."""
+    import torch
+
+    import rtgpu
+    import scenes
+
+    tmp = tempfile.mkdtemp(prefix="query_bench_")
+    xml = scenes.synthetic_heightfield(tmp, K=args.K, width=args.width, height=args.height)
+    os.chdir(tmp)
+    hs = rtgpu.HostScene(xml)
+    ds = rtgpu.DeviceScene(hs, 0)
+    w, h = args.width, args.height
+    n = w * h
+    dev = torch.device("cuda:0")
+    st = torch.cuda.current_stream().cuda_stream
+    rays = torch.empty((n, 8), dtype=torch.float32, device=dev)
+    ds.camera_rays_device(rays.data_ptr(), stream=st)
+    torch.cuda.synchronize()
+    g = torch.Generator(device="cpu").manual_seed(1234)
+    sets = {"pixel order": rays, "permuted": rays[torch.randperm(n, generator=g).to(dev)].contiguous()}
+    ks = (1, 2, 4, 8)
+    hits = torch.empty((n, max(ks), 4), dtype=torch.int32, device=dev)
+    cnt = torch.empty((n,), dtype=torch.int32, device=dev)
+    closest = torch.empty((n, 4), dtype=torch.int32, device=dev)
+    cases = [(f"trace_device (closest, no hint), {which}", which, 0) for which in sets]
+    cases += [(f"multi k = {k}, {which}", which, k) for which in sets for k in ks]
+
+    def run(which, k, reps):
+        buf = sets[which]
+        for _ in range(reps):
+            if k:
+                ds.trace_multi_device(buf.data_ptr(), n, k, hits.data_ptr(), cnt.data_ptr(), stream=st)
+            else:
+                ds.trace_device(buf.data_ptr(), n, closest.data_ptr(), stream=st)
+
+    # the answers first: k = 1 is the closest hit bit for bit; slot 0 of a longer list is too, except
+    # on near ties (a larger minT culls fewer boxes, and a face one ulp nearer behind a box the
+    # closest-hit walk culls is found): there the distances agree within 1e-4 relative
+    held, ties = {}, {}
+    for which in sets:
+        run(which, 0, 1)
+        for k in ks:
+            run(which, k, 1)
+            torch.cuda.synchronize()
+            first = hits.view(-1, 4)[: n * k].view(n, k, 4)[:, 0, :]
+            differ = (first[:, :3] != closest[:, :3]).any(1)
+            ta, tb = first[differ, 0].view(torch.float32), closest[differ, 0].view(torch.float32)
+            assert (k > 1 or not differ.any()) and bool(((ta - tb).abs() <= 1e-4 * tb.abs().clamp(min=1.0)).all()), (which, k)
+            held[which, k], ties[which, k] = float(cnt.float().mean()), int(differ.sum())
+    for _, which, k in cases:
+        run(which, k, args.warmup)
+    torch.cuda.synchronize()
+    ms = {c[0]: [] for c in cases}
+    for _ in range(args.reps):
+        for label, which, k in cases:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            run(which, k, args.launches)
+            e1.record()
+            e1.synchronize()
+            ms[label].append(e0.elapsed_time(e1) / args.launches)
+    lines = [f"multi: synthetic_heightfield K={args.K} {w}x{h}, {n} rays, {args.launches} launches x {args.reps} interleaved "
+             f"repetitions, device {torch.cuda.get_device_name(0)} (slot 0 of every case checked against trace_device: "
+             f"equal but for {max(ties.values())} near-tie rays at most)",
+             f"{'case':44s} {'ms (median)':>12s} {'min':>8s} {'max':>8s} {'Grays/s':>9s} {'hits held':>10s}"]
+    for label, which, k in cases:
+        v = ms[label]
+        lines.append(f"{label:44s} {np.median(v):12.4f} {min(v):8.4f} {max(v):8.4f} {n / np.median(v) / 1e6:9.3f} "
+                     f"{held[which, k] if k else float('nan'):10.3f}")
+    spread = lambda v: (max(v) - min(v)) / np.median(v) * 100
+    lines.append("spread over the repetitions: " + ", ".join(f"{spread(ms[c[0]]):.1f} %" for c in cases))
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--setups", type=int, default=9, help="update section: calls per set-up time")
@@ -383,6 +463,8 @@ def main():
         text += surface_main(args)
     if "update" in sections:
         text += update_main(args)
+    if "multi" in sections:
+        text += multi_main(args)
     text = "\n".join(text)
     print(text)
     if out:
