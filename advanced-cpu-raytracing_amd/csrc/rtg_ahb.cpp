@@ -295,82 +295,112 @@ int build_ahb(const std::vector<float4>& nodes, const std::vector<int2>& ext, in
         }
     }
     if (P.empty()) return -1;
-    Builder B(P);
-    int root;
+    // Collapse a binary tree to 4 wide (open the inner child of largest surface area until four
+    // remain), emitting each leaf's faces as entries in depth-first order; node and entry indices
+    // are relative to `wn` / `we`.  Returns the root's index in `wn`, -2 if the leaf encoding
+    // cannot hold an entry index or count.
+    struct Emitted { std::vector<WNode> wn; std::vector<float4> we; long long entries = 0; int depth = 0, root = -1; };
+    auto emit = [&](const Builder& B, const std::vector<Prim>& P, int root, Emitted& E) -> int {
+        std::vector<WNode>& out = E.wn;
+        std::vector<float4>& entries = E.we;
+        struct Job { int bn, owner, slot, depth; };
+        std::vector<Job> jobs{{root, -1, 0, 1}};
+        int rootIdx = -1;
+        while (!jobs.empty()) {
+            const Job j = jobs.back();
+            jobs.pop_back();
+            std::vector<int> C;
+            if (B.N[j.bn].left < 0) C.push_back(j.bn);
+            else { C.push_back(B.N[j.bn].left); C.push_back(B.N[j.bn].right); }
+            while (C.size() < 4) {
+                int best = -1;
+                double ba = -1.0;
+                for (size_t k = 0; k < C.size(); ++k)
+                    if (B.N[C[k]].left >= 0 && area(B.N[C[k]].lo, B.N[C[k]].hi) > ba) {
+                        ba = area(B.N[C[k]].lo, B.N[C[k]].hi);
+                        best = (int)k;
+                    }
+                if (best < 0) break;
+                const int x = C[best];
+                C[best] = B.N[x].left;
+                C.insert(C.begin() + best + 1, B.N[x].right);
+            }
+            const int w = (int)out.size();
+            out.emplace_back();
+            E.depth = std::max(E.depth, j.depth);
+            float* lo[3] = {&out[w].lox.x, &out[w].loy.x, &out[w].loz.x};
+            float* hi[3] = {&out[w].hix.x, &out[w].hiy.x, &out[w].hiz.x};
+            int* ch = &out[w].child.x;
+            int* lf = &out[w].leaf.x;
+            for (int k = 0; k < 4; ++k) {
+                if (k >= (int)C.size()) {
+                    for (int a = 0; a < 3; ++a) { lo[a][k] = INFINITY; hi[a][k] = -INFINITY; }
+                    ch[k] = WCHILD_EMPTY;
+                    lf[k] = 0;
+                    continue;
+                }
+                const BNode& n = B.N[C[k]];
+                for (int a = 0; a < 3; ++a) { lo[a][k] = n.lo[a]; hi[a][k] = n.hi[a]; }
+                if (n.left >= 0) {
+                    ch[k] = WCHILD_EMPTY;      // set when the child node is emitted
+                    lf[k] = 0;
+                    continue;
+                }
+                const size_t e0 = entries.size() / 3;
+                for (int q = n.pbeg; q < n.pbeg + n.pcnt; ++q)
+                    for (int f = P[q].first; f < P[q].first + P[q].count; ++f) {
+                        // [0].w: the face's reference leaf node; [1].w: the face itself (global
+                        // BVH-order index: the closest-hit walk reports it and orders ties by it)
+                        float4 A = tris[3 * (size_t)f], E1 = tris[3 * (size_t)f + 1];
+                        std::memcpy(&A.w, &P[q].ref, 4);
+                        std::memcpy(&E1.w, &f, 4);
+                        entries.push_back(A);
+                        entries.push_back(E1);
+                        entries.push_back(tris[3 * (size_t)f + 2]);
+                    }
+                const size_t cnt = entries.size() / 3 - e0;
+                if (cnt > 255) return -2;
+                ch[k] = -2;
+                lf[k] = (int)((e0 << 8) | cnt);
+                E.entries += (long long)cnt;
+            }
+            if (j.owner >= 0) (&out[j.owner].child.x)[j.slot] = w;
+            else rootIdx = w;
+            for (int k = (int)C.size() - 1; k >= 0; --k)
+                if (B.N[C[k]].left >= 0) jobs.push_back({C[k], w, k, j.depth + 1});
+        }
+        E.root = rootIdx;
+        return rootIdx;
+    };
+    Emitted E;
     if (mode == AHB_REF) {
+        Builder B(P);
         int pcur = 0;
-        root = B.from_reference(nodes, node_begin, pcur, chunks);
+        if (emit(B, P, B.from_reference(nodes, node_begin, pcur, chunks), E) == -2) return -2;
     } else {
-        root = B.build(0, (int)P.size());
+        Builder B(P);
+        if (emit(B, P, B.build(0, (int)P.size()), E) == -2) return -2;
     }
-    // collapse to 4 wide (open the inner child of largest surface area until four remain),
-    // emitting each leaf's faces as entries in depth-first order
-    struct Job { int bn, owner, slot, depth; };
-    std::vector<Job> jobs{{root, -1, 0, 1}};
-    int rootIdx = -1;
-    while (!jobs.empty()) {
-        const Job j = jobs.back();
-        jobs.pop_back();
-        std::vector<int> C;
-        if (B.N[j.bn].left < 0) C.push_back(j.bn);
-        else { C.push_back(B.N[j.bn].left); C.push_back(B.N[j.bn].right); }
-        while (C.size() < 4) {
-            int best = -1;
-            double ba = -1.0;
-            for (size_t k = 0; k < C.size(); ++k)
-                if (B.N[C[k]].left >= 0 && area(B.N[C[k]].lo, B.N[C[k]].hi) > ba) {
-                    ba = area(B.N[C[k]].lo, B.N[C[k]].hi);
-                    best = (int)k;
-                }
-            if (best < 0) break;
-            const int x = C[best];
-            C[best] = B.N[x].left;
-            C.insert(C.begin() + best + 1, B.N[x].right);
-        }
-        const int w = (int)out.size();
-        out.emplace_back();
-        if (st) { ++st->nodes; st->max_depth = std::max(st->max_depth, j.depth); }
-        float* lo[3] = {&out[w].lox.x, &out[w].loy.x, &out[w].loz.x};
-        float* hi[3] = {&out[w].hix.x, &out[w].hiy.x, &out[w].hiz.x};
-        int* ch = &out[w].child.x;
-        int* lf = &out[w].leaf.x;
+    // append, node and entry indices moved to their places in `out` / `entries`
+    const int nbase = (int)out.size();
+    const size_t ebase = entries.size() / 3;
+    if (ebase + E.we.size() / 3 > (1u << 23)) return -2;   // entry index out of the leaf encoding
+    for (WNode& W : E.wn) {
+        int* ch = &W.child.x;
+        int* lf = &W.leaf.x;
         for (int k = 0; k < 4; ++k) {
-            if (k >= (int)C.size()) {
-                for (int a = 0; a < 3; ++a) { lo[a][k] = INFINITY; hi[a][k] = -INFINITY; }
-                ch[k] = WCHILD_EMPTY;
-                lf[k] = 0;
-                continue;
-            }
-            const BNode& n = B.N[C[k]];
-            for (int a = 0; a < 3; ++a) { lo[a][k] = n.lo[a]; hi[a][k] = n.hi[a]; }
-            if (n.left >= 0) {
-                ch[k] = WCHILD_EMPTY;      // set when the child node is emitted
-                lf[k] = 0;
-                continue;
-            }
-            const size_t e0 = entries.size() / 3;
-            for (int q = n.pbeg; q < n.pbeg + n.pcnt; ++q)
-                for (int f = P[q].first; f < P[q].first + P[q].count; ++f) {
-                    // [0].w: the face's reference leaf node; [1].w: the face itself (global
-                    // BVH-order index: the closest-hit walk reports it and orders ties by it)
-                    float4 A = tris[3 * (size_t)f], E1 = tris[3 * (size_t)f + 1];
-                    std::memcpy(&A.w, &P[q].ref, 4);
-                    std::memcpy(&E1.w, &f, 4);
-                    entries.push_back(A);
-                    entries.push_back(E1);
-                    entries.push_back(tris[3 * (size_t)f + 2]);
-                }
-            const size_t cnt = entries.size() / 3 - e0;
-            if (e0 >= (1u << 23) || cnt > 255) return -2;   // entry index / count out of the leaf encoding
-            ch[k] = -2;
-            lf[k] = (int)((e0 << 8) | cnt);
-            if (st) st->entries += (long long)cnt;
+            if (ch[k] >= 0) ch[k] += nbase;
+            else if (ch[k] == -2) lf[k] += (int)(ebase << 8);
         }
-        if (j.owner >= 0) (&out[j.owner].child.x)[j.slot] = w;
-        else rootIdx = w;
-        for (int k = (int)C.size() - 1; k >= 0; --k)
-            if (B.N[C[k]].left >= 0) jobs.push_back({C[k], w, k, j.depth + 1});
+        out.push_back(W);
     }
+    entries.insert(entries.end(), E.we.begin(), E.we.end());
+    if (st) {
+        st->nodes += (long long)E.wn.size();
+        st->entries += E.entries;
+        st->max_depth = std::max(st->max_depth, E.depth);
+    }
+    const int rootIdx = E.root < 0 ? -1 : E.root + nbase;
     return rootIdx;
 }
 

@@ -39,16 +39,20 @@ DEV void list_init(HitList<KMAX>& L, float tmax) {
     }
 }
 // A compare-and-carry chain from slot 0 up: the new hit takes the first slot whose t it is
-// strictly below and carries that slot's hit on, so it lands after every held hit of equal t
-// (ties stable: first object, first face of the walk); what leaves slot k - 1 is dropped.
-// Returns the new minT, slot k - 1 (k is wave-uniform: scalar compares).
+// strictly below, so it lands after every held hit of equal t (ties stable: first object, first
+// face of the walk), and from there on every slot's hit moves up by one, whatever its t: a
+// carried hit that ties with the next slot was found before it and stays before it (compared
+// again, it would stay behind and be dropped in place of the later one).  What leaves slot
+// k - 1 is dropped.  Returns the new minT, slot k - 1 (k is wave-uniform: scalar compares).
 template <int KMAX>
 DEV float list_insert(HitList<KMAX>& L, const int k, float t, int obj, int face) {
     float minT = L.t[0];
+    bool placed = false;
 #pragma unroll
     for (int j = 0; j < KMAX; ++j) {
         if (j < k) {
-            const bool lt = t < L.t[j];
+            const bool lt = placed | (t < L.t[j]);
+            placed = lt;
             const float ct = L.t[j];
             const int co = L.obj[j], cf = L.face[j];
             L.t[j] = lt ? t : ct;

@@ -164,12 +164,35 @@ bool anyhit_trees(const rtg_scene_desc* d, const std::vector<float4>& nd, const 
                                       (hi[2] - lo[2]) * (hi[2] - lo[2]));
         reach[o.mesh] = std::max(reach[o.mesh], diag);
     }
-    aroot.assign(d->num_meshes, -1);
-    bool ahbOk = true;
-    for (int m = 0; m < d->num_meshes && ahbOk; ++m) {
-        if (meshEnd[m] <= meshBegin[m]) continue;
-        aroot[m] = build_ahb(nd, nx, meshBegin[m], meshEnd[m], htp, reach[m], (AhbMode)mode, anodes, ahtris, &ast);
-        if (aroot[m] == -2) ahbOk = false;      // leaf encoding exceeded: shadow rays take the reference walk
+    auto build_all = [&](AhbMode md, std::vector<WNode>& wn, std::vector<float4>& we, std::vector<int>& roots,
+                         AhbStats& st) {
+        roots.assign(d->num_meshes, -1);
+        for (int m = 0; m < d->num_meshes; ++m) {
+            if (meshEnd[m] <= meshBegin[m]) continue;
+            roots[m] = build_ahb(nd, nx, meshBegin[m], meshEnd[m], htp, reach[m], md, wn, we, &st);
+            if (roots[m] == -2) return false;   // leaf encoding exceeded: shadow rays take the reference walk
+        }
+        return true;
+    };
+    const bool fresh = anodes.empty() && ahtris.empty();
+    const AhbStats ast0 = ast;
+    bool ahbOk = build_all((AhbMode)mode, anodes, ahtris, aroot, ast);
+    // The binned SAH is a heuristic: on some scenes (long runs of equal boxes, one outlier that
+    // stretches the bins) its trees have more wide nodes than the reference's own topology
+    // collapsed.  The default trees are never the larger set: a scene on which the SAH loses
+    // takes the reference's topology over the same primitives and cull boxes, so the walk's
+    // decisions are what they were.  (The split tree has other primitives and keeps the SAH.)
+    if (ahbOk && fresh && mode == AHB_EXACT) {
+        std::vector<WNode> rn;
+        std::vector<float4> re;
+        std::vector<int> rr;
+        AhbStats rs = ast0;
+        if (build_all(AHB_REF, rn, re, rr, rs) && rs.nodes < ast.nodes) {
+            anodes.swap(rn);
+            ahtris.swap(re);
+            aroot.swap(rr);
+            ast = rs;
+        }
     }
     if (!ahbOk) { anodes.clear(); ahtris.clear(); aroot.assign(d->num_meshes, -1); }
     return ahbOk;

@@ -14,9 +14,11 @@ No case has a zero-area face.  What each case is for:
 
   spread_<n>        1, 2, 3, 63, 64, 65, 255, 256, 257, 513 well-spread faces: the scans with
                     n = 1, the wave-uniform and mixed paths of the child-box reduction
-  copies_<n>        n copies of one triangle, n in 2, 8, 9, 254, 255, 256, 300: all centroids are equal
+  copies_<n>        n copies of one triangle, n in 2, 8, 9, 16, 17, 254, 255, 256, 300: all centroids are equal
                     and above the split, so every face is big, the root stays a leaf in the order the
-                    swap loop leaves behind, and the leaf word crosses the 254 / 255 packing boundary
+                    swap loop leaves behind, and the leaf word crosses the 254 / 255 packing boundary;
+                    8 / 9 and 16 / 17 sit either side of the walks' large-leaf and deferred-leaf
+                    thresholds (kBigLeaf, kDeferLeaf)
   nested_256        256 different triangles whose centroids share x = the split: as copies_256, but
                     the order the loop leaves behind shows in the face records
   lattice           one cell for every big / small pattern of length 2..8 with both halves non-empty
@@ -248,7 +250,7 @@ def _case(fn, *a):
 CASES = {}
 for _n in (1, 2, 3, 63, 64, 65, 255, 256, 257, 513):
     CASES[f"spread_{_n}"] = _case(spread, _n)
-for _n in (2, 8, 9, 254, 255, 256, 300):
+for _n in (2, 8, 9, 16, 17, 254, 255, 256, 300):
     CASES[f"copies_{_n}"] = _case(copies, _n)
 CASES["nested_256"] = _case(nested, 256)
 CASES["lattice"] = _case(lattice)

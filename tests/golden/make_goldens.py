@@ -15,6 +15,8 @@ Fixture scenes live in tests/golden/scenes/: copies of the reference's own scene
     python tests/golden/make_goldens.py radiance_rays   # only the radiance-ray goldens
                                                         # (radiance_rays_<scene>.npz)
     python tests/golden/make_goldens.py bvh        # only the BVH goldens (bvh_<case>.npz, bvh_manifest.json)
+    python tests/golden/make_goldens.py walk_rays  # only the walk goldens (walk_rays_<case>.npz,
+                                                   # walk_rays_manifest.json)
 """
 import hashlib
 import json
@@ -1126,11 +1128,93 @@ def make_bvh(names=None):
         json.dump(man, f, indent=1, sort_keys=True)
 
 
+# Walk goldens (walk_rays_<case>.npz): the edge, aimed and light rays of tests/walk_cases.py on the
+# adversarial meshes of tests/bvh_cases.py through the reference's own Shape::Intersect (refdriver
+# rays), closest hit and occlusion.  rays, labels (walk_cases.SETS), index (the ray's position in
+# walk_cases.ray_sets' output: a drifting generator fails loudly), has_hit, t_bits, position,
+# occluded, sha256 (Case.vertex_sha256).  walk_rays_manifest.json lists the cases, what was
+# dropped (a set whose two runs differ, or the whole case if the reference does not return) and how
+# many rays the seeded subsample kept where all of them would exceed BVH_MAX_BYTES.
+def run_ref_rays_in(cwd, xml, rays):
+    """run_ref_rays on <cwd>/<xml>."""
+    src, dst = os.path.join(cwd, "_rays_in.bin"), os.path.join(cwd, "_rays_out.bin")
+    rays.tofile(src)
+    try:
+        rc = subprocess.run([DRIVER, "rays", xml, src, dst], cwd=cwd, stdout=subprocess.DEVNULL, timeout=600).returncode
+        if rc != 0:
+            return None
+        raw = open(dst, "rb").read()
+    except subprocess.TimeoutExpired:
+        return None
+    assert raw[:4] == b"RTGQ" and np.frombuffer(raw[4:8], np.int32)[0] == rays.size
+    return np.frombuffer(raw[8:], np.int32).reshape(-1, 4).copy()
+
+
+def make_walk_rays(names=None):
+    import tempfile
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import edge_rays
+    import walk_cases
+    path = os.path.join(HERE, "walk_rays_manifest.json")
+    man = json.load(open(path)) if names and os.path.exists(path) else {"cases": {}, "dropped": {}}
+    for name in names or walk_cases.RECORDED:
+        case = walk_cases.get(name)
+        man["cases"].pop(name, None)
+        man["dropped"].pop(name, None)
+        with tempfile.TemporaryDirectory() as d:
+            hs = walk_cases.load(d, name)
+            rays, labels = walk_cases.ray_sets(hs, name)
+            g = labels == edge_rays.CLASSES["G"]
+            ans = np.zeros((rays.size, 4), np.int32)
+            keep = np.ones(rays.size, bool)
+            dropped = []
+            for part in (~g, g):
+                a, b = run_ref_rays_in(d, name + ".xml", rays[part]), run_ref_rays_in(d, name + ".xml", rays[part])
+                if a is None or b is None:
+                    keep &= ~part
+                    dropped.append("G (no return)" if part is g else "every finite ray (no return)")
+                    continue
+                ans[part] = a
+                for c in np.unique(labels[part]):
+                    sel = labels[part] == c
+                    if not np.array_equal(a[sel], b[sel]):
+                        keep &= labels != c
+                        dropped.append(walk_cases.SET_NAMES[int(c)] + " (two runs differ)")
+        if not np.any(keep & ~g):
+            man["dropped"][name] = "the reference does not return"
+            print("walk rays", name, "dropped:", man["dropped"][name])
+            continue
+        # the edge rays whole; of the aimed and light rays a seeded choice that fits the size limit
+        edge = np.flatnonzero(keep & (labels < walk_cases.SETS["aimed"]))
+        rest = np.random.default_rng(20272).permutation(np.flatnonzero(keep & (labels >= walk_cases.SETS["aimed"])))
+        out = os.path.join(HERE, f"walk_rays_{name}.npz")
+        m = rest.size
+        while True:
+            idx = np.sort(np.concatenate([edge, rest[:m]]))
+            np.savez_compressed(out, rays=rays[idx], labels=labels[idx], index=idx.astype(np.int32),
+                                has_hit=ans[idx, 0].astype(np.int8), t_bits=ans[idx, 1].view(np.uint32),
+                                position=ans[idx, 2], occluded=ans[idx, 3].astype(np.int8),
+                                sha256=np.array(case.vertex_sha256()))
+            size = os.path.getsize(out)
+            if size <= BVH_MAX_BYTES:
+                break
+            assert m > 0, (name, size)
+            m = int(m * 0.8 * BVH_MAX_BYTES / size)
+        man["cases"][name] = {"sha256": case.vertex_sha256(), "rays": int(idx.size), "generated": int(rays.size),
+                              "kept_of_aimed_and_light": [int(m), int(rest.size)], "dropped_sets": dropped, "bytes": size}
+        print("walk rays", name, man["cases"][name])
+    with open(path, "w") as f:
+        json.dump(man, f, indent=1, sort_keys=True)
+
+
 def main():
     if not os.path.exists(DRIVER):
         sys.exit(f"{DRIVER} missing: build it with `make -C {os.path.join(ROOT, 'oracle')}` (needs /root/reference)")
     man = {}
     only = set(sys.argv[1:])
+    if only and all(o == "walk_rays" or o.startswith("walk_rays_") for o in only):
+        make_walk_rays(None if "walk_rays" in only else [o[len("walk_rays_"):] for o in sorted(only)])
+        return
     if only and all(o == "bvh" or o.startswith("bvh_") for o in only):
         make_bvh(None if "bvh" in only else [o[len("bvh_"):] for o in sorted(only)])
         return
@@ -1181,6 +1265,7 @@ def main():
         make_edge_rays(EDGE_SCENES)
         make_radiance_rays(RADIANCE_SCENES)
         make_bvh()
+        make_walk_rays()
 
 
 if __name__ == "__main__":

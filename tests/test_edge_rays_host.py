@@ -21,6 +21,7 @@ import edge_rays as er
 import oracle_bind as ob
 import query_util as qu
 import rtgpu
+import walk_cases as wc
 
 SCENES = os.path.join(ob.GOLDEN, "scenes")
 NAMES = ["simple", "spheres", "transforms_textures", "cornell_dielectric", "mesh_light", "dof_motion", "edge_lattice",
@@ -42,10 +43,6 @@ def load_golden(name):
     for a in g.values():
         a.setflags(write=False)
     return g
-
-
-def _names(rows, labels):
-    return [(int(i), er.NAMES[int(labels[i])]) for i in rows[:8]]
 
 
 @pytest.mark.parametrize("name", NAMES)
@@ -87,15 +84,7 @@ def test_host_equals_reference(name):
               "of them -0:", int(minus.any(1).sum()))
         assert zero.any(1).sum() >= 32 and minus.any(1).sum() >= 8
 
-    bad = np.flatnonzero((hits["object"] >= 0) != ref_hit)
-    assert bad.size == 0, (name, "hit flag", _names(bad, labels), rays[bad[:4]], hits[bad[:4]])
-    bad = np.flatnonzero(hits["t"].view(np.uint32) != g["t_bits"])
-    assert bad.size == 0, (name, "t bits", _names(bad, labels), rays[bad[:4]], hits[bad[:4]], g["t_bits"][bad[:4]])
-    bad = np.flatnonzero(hits["object"] != g["position"])
-    assert bad.size == 0, (name, "object", _names(bad, labels), hits[bad[:4]], g["position"][bad[:4]])
-    bad = np.flatnonzero((occ == 0) != (g["occluded"] != 0))
-    assert bad.size == 0, (name, "occlusion", _names(bad, labels), rays[bad[:4]])
-    assert set(np.unique(occ)) <= {0, -1}
+    wc.check_host_equals_reference(name, rays, labels, g, hits, occ)
 
 
 def _det3(c0, c1, c2):

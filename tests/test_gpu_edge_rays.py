@@ -56,6 +56,7 @@ import edge_rays as er
 import oracle_bind as ob
 import query_util as qu
 import rtgpu
+import walk_cases as wc
 
 pytestmark = pytest.mark.gpu
 
@@ -63,11 +64,7 @@ SCENES = os.path.join(ob.GOLDEN, "scenes")
 NAMES = ["edge_lattice", "edge_roof", "synth_10k", "simple", "spheres", "transforms_textures", "dof_motion",
          "mesh_light", "defer_gate"]
 GENERATED = ("synth_10k", "defer_gate")
-# (label, any_hit, coherent, normals)
-VARIANTS = [("trace", False, False, False), ("coherent", False, True, False), ("normals", False, False, True),
-            ("normals+coherent", False, True, True), ("any_hit", True, False, False),
-            ("any_hit+coherent", True, True, False)]
-MAX_CALL = 4096
+VARIANTS = wc.VARIANTS               # (label, any_hit, coherent, normals)
 
 _cache = {}
 
@@ -106,70 +103,14 @@ def _scene(name, tmp_path_factory):
     else:
         z = np.load(os.path.join(ob.GOLDEN, f"edge_rays_{name}.npz"), allow_pickle=False)
         rays, labels = z["rays"].view(rtgpu.RAY_DTYPE).reshape(-1), z["labels"]
-    pool = np.concatenate([rays, ds.camera_rays()])
-    h_hits, h_nrm = hs.trace(pool, normals=True)
-    h_occ = hs.trace(pool, any_hit=True)
-    sc = {"hs": hs, "ds": ds, "labels": labels, "pool": pool, "hits": h_hits, "nrm": h_nrm, "occ": h_occ,
-          "n_edge": rays.size}
-    for a in (labels, pool, h_hits, h_nrm, h_occ):
-        a.setflags(write=False)
+    sc = wc.device_pool(hs, ds, rays, labels)
     _cache[name] = sc
     return sc
 
 
-def _compare(name, cls, mix, sc, idx):
-    """Every variant of ds.trace on the pool rays `idx` against the host walk's answers, raw
-    bytes, at most MAX_CALL rays per call."""
-    idx = np.asarray(idx)
-    for b in range(0, idx.size, MAX_CALL):
-        sel = idx[b:b + MAX_CALL]
-        part = np.ascontiguousarray(sc["pool"][sel])
-        for label, any_hit, coherent, normals in VARIANTS:
-            where = (name, "class " + cls, mix, label)
-            got = sc["ds"].trace(part, any_hit=any_hit, coherent=coherent, normals=normals)
-            hits, nrm = got if normals else (got, None)
-            if any_hit:                       # the occlusion boolean (the t field is not part of the answer)
-                want = sc["occ"][sel]
-                bad = np.flatnonzero(hits["object"] != want["object"])
-            else:
-                want = sc["hits"][sel]
-                bad = np.flatnonzero((hits.view(np.uint32).reshape(-1, 4) != want.view(np.uint32).reshape(-1, 4)).any(1))
-            assert bad.size == 0, (where, "first differing rays (lane, pool index; edge rays are below %d)" % sc["n_edge"],
-                                   list(zip(((b + bad[:8]) % 64).tolist(), sel[bad[:8]].tolist())), part[bad[:4]],
-                                   "device", hits[bad[:4]], "host", want[bad[:4]])
-            if any_hit:
-                assert set(np.unique(hits["object"])) <= {0, -1}, where
-            if normals:
-                h_nrm = sc["nrm"][sel]
-                badn = np.flatnonzero((nrm.view(np.uint32) != h_nrm.view(np.uint32)).any(1))
-                assert badn.size == 0, (where, "normals", sel[badn[:8]], part[badn[:4]], nrm[badn[:4]], h_nrm[badn[:4]])
-    return idx.size
-
-
-def _one_per_wave(edge, n_edge, n_cam, rng):
-    """Waves of 63 consecutive camera rays and one edge ray: lane 0 in even waves, lane 63 in odd
-    ones."""
-    m = edge.size
-    out = n_edge + (rng.integers(n_cam, size=m)[:, None] + np.arange(64)[None]) % n_cam
-    out[np.arange(m), np.where(np.arange(m) % 2 == 0, 0, 63)] = edge
-    return out.reshape(-1)
-
-
-def _half_waves(edge, n_edge, n_cam, rng):
-    """Edge and camera rays in alternate lanes: 32 edge lanes per wave."""
-    m = edge.size
-    out = np.empty(2 * m, np.int64)
-    out[0::2] = edge
-    out[1::2] = n_edge + (rng.integers(n_cam) + np.arange(m)) % n_cam
-    return out
-
-
-def _mixes(name, cls, sc, edge, rng):
-    n_edge, n_cam = sc["n_edge"], sc["pool"].size - sc["n_edge"]
-    n = _compare(name, cls, "alone", sc, edge)
-    n += _compare(name, cls, "1 edge lane per 64", sc, _one_per_wave(edge, n_edge, n_cam, rng))
-    n += _compare(name, cls, "32 edge lanes per 64", sc, _half_waves(edge, n_edge, n_cam, rng))
-    return n
+# the comparison and the wave mixes are shared with test_gpu_walk_cases.py (walk_cases.py)
+_compare = wc.compare_device
+_mixes = wc.mixes
 
 
 @pytest.mark.parametrize("name", NAMES)
