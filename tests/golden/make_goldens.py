@@ -84,6 +84,12 @@ FIXTURES = {
     # instancedMesh.hpp:23) and segfaults once the heap garbage is out of range; C4 is
     # checked GPU vs the CPU restatement (tests/test_gpu_parity.py).
     "c5_dragon": ("generated", 192, 108, "exact", None),
+    # ray trees above depth 8 (the 32-frame stacks): rooms of tests/variant_scenes.py -- the closed
+    # mirror and conductor corridor at depths 9 and 32 (one ray per level, every level in use) and
+    # the single dielectric sphere with Beer absorption at depth 12
+    "deep_mirrors_9": ("generated", 96, 64, "exact", None),
+    "deep_mirrors_32": ("generated", 96, 64, "exact", None),
+    "deep_glass_12": ("generated", 96, 64, "exact", None),
 }
 
 
@@ -688,6 +694,11 @@ def prepare(name, src, w, h, edits):
             gen.config_c3(SCENES, K=12000, width=w, height=h, spp=1)
         elif name == "c5_dragon":
             gen.config_c5(SCENES, K=30000, width=w, height=h, spp=1)
+        elif name.startswith("deep_"):
+            sys.path.insert(0, os.path.join(ROOT, "tests"))
+            import variant_scenes
+            assert (variant_scenes.DEEP[name]["width"], variant_scenes.DEEP[name]["height"]) == (w, h)
+            variant_scenes.write_deep(SCENES, name)
         return dst
     if src == "authored":
         gen.with_resolution(dst, dst, w, h)
@@ -997,7 +1008,8 @@ def make_edge_rays(names):
 # eyes.  The scenes whose render golden is `exact` and that between them cover the shading, and
 # edge_roof for its instance.
 RADIANCE_SCENES = ("simple", "spheres_mirror", "cornell_dielectric", "cornell_conductors", "brdf_lights", "image_tex",
-                   "transforms_textures", "bump_normal", "scienceTree_diamond", "edge_roof")
+                   "transforms_textures", "bump_normal", "scienceTree_diamond", "edge_roof", "deep_mirrors_9",
+                   "deep_mirrors_32", "deep_glass_12")
 RADIANCE_MAX_DROP = 0.01          # of a scene's rays; and no whole class
 RADIANCE_MAX_BYTES = 64 * 1024
 

@@ -47,7 +47,8 @@ M_TIMES = np.array([0.0, 0.25, 0.75, 1.0 - 2.0 ** -24], f32)
 GRAZE_DEG = 0.1
 # the scenes with a golden (tests/golden/radiance_rays_<scene>.npz, `make_goldens.py radiance_rays`)
 GOLDEN_SCENES = ["simple", "spheres_mirror", "cornell_dielectric", "cornell_conductors", "brdf_lights", "image_tex",
-                 "transforms_textures", "bump_normal", "scienceTree_diamond", "edge_roof"]
+                 "transforms_textures", "bump_normal", "scienceTree_diamond", "edge_roof", "deep_mirrors_9",
+                 "deep_mirrors_32", "deep_glass_12"]
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
