@@ -13,6 +13,9 @@
 //
 // rtg_desc_trace_rays_multi: the same walk with the ray keeping its k smallest accepted distances
 // (multi_one below) -- the same box_hit / face_hit and sphere arithmetic, minT the k-th distance.
+//
+// rtg_desc_closest_points: the nearest surface point to a point (closest_one below).  No reference
+// code stands behind it: this walk is the definition that k_closest (rtg_closest.hip) repeats.
 #include "host_query.hpp"
 
 #include <algorithm>
@@ -21,6 +24,7 @@
 #include <vector>
 
 #include "host_math.hpp"
+#include "rtg_pointxf.hpp"
 
 namespace rtg {
 namespace {
@@ -328,6 +332,171 @@ void multi_one(const rtg_scene_desc* d, const rtg_ray& q, int kk, rtg_hit* out, 
     if (count) *count = L.n;
 }
 
+// ---- closest-point queries (rtg_desc_closest_points): the nearest surface point to a point.
+// No ray and no reference code: rtgpu.h states the semantics, this walk defines them operation by
+// operation, and k_closest (rtg_closest.hip) repeats its decisions with the same arithmetic.
+
+// The held candidate.  Everything is compared on the squared distance; among equal ones the
+// lexicographically smaller (object, face) stays.  With nothing held obj is -1, below every
+// candidate's, so only d2 < best accepts; a NaN d2 fails both comparisons.
+struct Nearest {
+    float d2;
+    int obj = -1, face = -1;
+    V3 c;
+    void offer(float nd2, int o, int f, const V3& nc) {
+        if (nd2 < d2 || (nd2 == d2 && (o < obj || (o == obj && f < face)))) {
+            d2 = nd2; obj = o; face = f; c = nc;
+        }
+    }
+};
+
+V3 xf_point(const float* m, const V3& v) {
+    return V3(((m[0] * v.x + m[1] * v.y) + m[2] * v.z) + m[3], ((m[4] * v.x + m[5] * v.y) + m[6] * v.z) + m[7],
+              ((m[8] * v.x + m[9] * v.y) + m[10] * v.z) + m[11]);
+}
+V3 xf_vector(const float* m, const V3& v) {
+    return V3((m[0] * v.x + m[1] * v.y) + m[2] * v.z, (m[4] * v.x + m[5] * v.y) + m[6] * v.z,
+              (m[8] * v.x + m[9] * v.y) + m[10] * v.z);
+}
+
+// squared distance from p to the box; fmaxf drops a NaN operand
+float box_d2(const float* mn, const float* mx, const V3& p) {
+    const float ex = fmaxf(fmaxf(mn[0] - p.x, p.x - mx[0]), 0.f);
+    const float ey = fmaxf(fmaxf(mn[1] - p.y, p.y - mx[1]), 0.f);
+    const float ez = fmaxf(fmaxf(mn[2] - p.z, p.z - mx[2]), 0.f);
+    return (ex * ex + ey * ey) + ez * ez;
+}
+
+// Closest point of the triangle (a, a + ab, a + ac) to p by its Voronoi regions (Ericson,
+// Real-Time Collision Detection 5.1.5), regions in the order A, B, AB, C, AC, BC, interior;
+// c = a + ab v + ac w.  Returns the squared distance.
+float tri_closest(const V3& a, const V3& ab, const V3& ac, const V3& p, V3& c) {
+    const V3 ap = p - a;
+    const V3 bp = ap - ab;
+    const V3 cp = ap - ac;
+    const float d1 = dot(ab, ap), d2 = dot(ac, ap);
+    const float d3 = dot(ab, bp), d4 = dot(ac, bp);
+    const float d5 = dot(ab, cp), d6 = dot(ac, cp);
+    const float vc = d1 * d4 - d3 * d2;
+    const float vb = d5 * d2 - d1 * d6;
+    const float va = d3 * d6 - d5 * d4;
+    float v, w;
+    if (d1 <= 0.f && d2 <= 0.f) { v = 0.f; w = 0.f; }
+    else if (d3 >= 0.f && d4 <= d3) { v = 1.f; w = 0.f; }
+    else if (vc <= 0.f && d1 >= 0.f && d3 <= 0.f) { v = d1 / (d1 - d3); w = 0.f; }
+    else if (d6 >= 0.f && d5 <= d6) { v = 0.f; w = 1.f; }
+    else if (vb <= 0.f && d2 >= 0.f && d6 <= 0.f) { v = 0.f; w = d2 / (d2 - d6); }
+    else if (va <= 0.f && (d4 - d3) >= 0.f && (d5 - d6) >= 0.f) {
+        w = (d4 - d3) / ((d4 - d3) + (d5 - d6));
+        v = 1.f - w;
+    } else {
+        const float den = 1.f / ((va + vb) + vc);
+        v = vb * den;
+        w = vc * den;
+    }
+    c = (a + ab * v) + ac * w;
+    const V3 d = p - c;
+    return dot(d, d);
+}
+
+struct PointWalk {
+    const rtg_bvh_node* nodes;
+    const rtg_face* faces;
+    const PointXf* X;
+    V3 p, pl;                     // the world point; the point the boxes are tested against
+    Nearest* best;
+    int obj, face_offset;
+};
+
+// every face of a leaf, in order: the walk record's {v0, v0 - v1, v0 - v2} (the differences
+// formed in float first, as face_tables / k_write_faces store them), carried to world space
+void closest_leaf(PointWalk& w, const rtg_bvh_node& n) {
+    for (int i = n.first; i < n.first + n.count; ++i) {
+        const rtg_face& F = w.faces[i];
+        V3 a = from_f3(F.v0);
+        const float e1x = F.v0.x - F.v1.x, e1y = F.v0.y - F.v1.y, e1z = F.v0.z - F.v1.z;
+        const float e2x = F.v0.x - F.v2.x, e2y = F.v0.y - F.v2.y, e2z = F.v0.z - F.v2.z;
+        V3 ab(-e1x, -e1y, -e1z), ac(-e2x, -e2y, -e2z);
+        if (!(w.X->flags & PXF_IDENTITY)) {
+            a = xf_point(w.X->fwd, a);
+            ab = xf_vector(w.X->fwd, ab);
+            ac = xf_vector(w.X->fwd, ac);
+        }
+        V3 c;
+        const float d2 = tri_closest(a, ab, ac, w.p, c);
+        w.best->offer(d2, w.obj, w.face_offset + i, c);
+    }
+}
+
+// pass 2: the pre-order walk, a node skipped iff its box is farther than the held distance
+// (local d2 <= lip2 * world d2); a false comparison descends
+void closest_bvh(PointWalk& w, int k) {
+    const rtg_bvh_node& n = w.nodes[k];
+    if (box_d2(n.bmin, n.bmax, w.pl) > w.best->d2 * w.X->lip2) return;
+    if (n.left < 0) {
+        closest_leaf(w, n);
+    } else {
+        closest_bvh(w, n.left);
+        closest_bvh(w, n.left + 1);
+    }
+}
+
+void closest_one(const rtg_scene_desc* d, const PointXf* xf, const rtg_point& q, rtg_nearest& out) {
+    const V3 p(q.x, q.y, q.z);
+    Nearest best;
+    best.d2 = q.max_dist * q.max_dist;
+    const bool finite = fabsf(q.x) < INFINITY && fabsf(q.y) < INFINITY && fabsf(q.z) < INFINITY;
+    for (int k = 0; finite && k < d->num_objects; ++k) {
+        const rtg_object& ob = d->objects[k];
+        const PointXf& X = xf[k];
+        if (ob.kind == RTG_OBJ_SPHERE) {
+            V3 centre = from_f3(ob.center);
+            float radius = ob.radius;
+            if (!(X.flags & PXF_IDENTITY)) {
+                centre = xf_point(X.fwd, centre);
+                radius = radius * X.scale;
+            }
+            const V3 v = p - centre;
+            const float l = sqrtf(dot(v, v));
+            const float dd = fabsf(l - radius);
+            const V3 c = l == 0.f ? centre + V3(radius, 0.f, 0.f) : centre + v * (radius / l);
+            best.offer(dd * dd, k, -1, c);
+            continue;
+        }
+        const rtg_mesh& M = d->meshes[ob.mesh];
+        if (M.node_count <= 0) continue;
+        PointWalk w;
+        w.nodes = d->nodes + M.node_offset;
+        w.faces = d->faces + M.face_offset;
+        w.X = &X;
+        w.p = p;
+        w.pl = (X.flags & PXF_IDENTITY) ? p : xf_point(X.inv, p);
+        w.best = &best;
+        w.obj = k;
+        w.face_offset = M.face_offset;
+        // pass 1: descend to the leaf whose boxes are nearer at every level (a tie, or a false
+        // comparison, goes left), for a tight bound before the pruned walk (without it an
+        // unbounded query tests faces in pre-order until it happens on a near one: DESIGN.md 5)
+        int i = 0;
+        while (w.nodes[i].left >= 0) {
+            const rtg_bvh_node& l = w.nodes[w.nodes[i].left];
+            const rtg_bvh_node& r = w.nodes[w.nodes[i].left + 1];
+            i = box_d2(r.bmin, r.bmax, w.pl) < box_d2(l.bmin, l.bmax, w.pl) ? w.nodes[i].left + 1 : w.nodes[i].left;
+        }
+        closest_leaf(w, w.nodes[i]);
+        closest_bvh(w, 0);
+    }
+    const bool hit = best.obj >= 0;
+    out.dist = hit ? sqrtf(best.d2) : q.max_dist;
+    out.object = best.obj;
+    out.face = best.face;
+    out.pad0 = 0;
+    out.px = hit ? best.c.x : 0.f;
+    out.py = hit ? best.c.y : 0.f;
+    out.pz = hit ? best.c.z : 0.f;
+    out.pad1 = 0.f;
+}
+
 // fn(begin, end) over [0, n) in contiguous chunks on a few threads: rays are independent
 template <typename Fn>
 void chunked(int64_t n, Fn&& work) {
@@ -371,6 +540,32 @@ int host_trace_rays_multi(const rtg_scene_desc* d, const rtg_ray* rays, int64_t 
     if (!rays || !hits) { err = "null buffer"; return RTG_ERR_INVALID; }
     chunked(n, [&](int64_t b, int64_t e) {
         for (int64_t i = b; i < e; ++i) multi_one(d, rays[i], k, hits + i * k, counts ? counts + i : nullptr);
+    });
+    return RTG_OK;
+}
+
+int closest_unsupported(const PointXf* xf, int num_objects, std::string& err) {
+    for (int i = 0; i < num_objects; ++i)
+        if (!(xf[i].flags & PXF_SPHERE_OK)) {
+            err = "object " + std::to_string(i) + ": a sphere under a transform that is not a similarity is an "
+                  "ellipsoid, which closest-point queries do not handle";
+            return RTG_ERR_UNSUPPORTED;
+        }
+    return RTG_OK;
+}
+
+int host_closest_points(const rtg_scene_desc* d, const rtg_point* points, int64_t n, uint32_t flags, rtg_nearest* out,
+                        std::string& err) {
+    if (!d) { err = "null description"; return RTG_ERR_INVALID; }
+    if (n < 0 || n > INT32_MAX) { err = "point count out of range"; return RTG_ERR_INVALID; }
+    if (flags) { err = "unknown query flags"; return RTG_ERR_INVALID; }
+    if (const char* e = check_desc(d)) { err = e; return RTG_ERR_INVALID; }
+    if (n > 0 && (!points || !out)) { err = "null buffer"; return RTG_ERR_INVALID; }
+    std::vector<PointXf> xf((size_t)d->num_objects);
+    for (int i = 0; i < d->num_objects; ++i) point_xf_record(d->objects[i], xf[i]);
+    if (int rc = closest_unsupported(xf.data(), d->num_objects, err)) return rc;
+    chunked(n, [&](int64_t b, int64_t e) {
+        for (int64_t i = b; i < e; ++i) closest_one(d, xf.data(), points[i], out[i]);
     });
     return RTG_OK;
 }

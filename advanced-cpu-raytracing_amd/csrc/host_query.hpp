@@ -19,4 +19,13 @@ int host_trace_rays(const rtg_scene_desc* d, const rtg_ray* rays, int64_t n, uin
 int host_trace_rays_multi(const rtg_scene_desc* d, const rtg_ray* rays, int64_t n, int32_t k, uint32_t flags,
                           rtg_hit* hits, int32_t* counts, std::string& err);
 
+// Closest-point queries (rtgpu.h rtg_desc_closest_points): the nearest surface point to each
+// point, by the walk that defines the query (the yardstick of k_closest, bit for bit).
+int host_closest_points(const rtg_scene_desc* d, const rtg_point* points, int64_t n, uint32_t flags, rtg_nearest* out,
+                        std::string& err);
+// RTG_OK, or RTG_ERR_UNSUPPORTED with the message naming the first object whose record lacks
+// PXF_SPHERE_OK (a sphere that the scene's transform makes an ellipsoid).
+struct PointXf;
+int closest_unsupported(const PointXf* xf, int num_objects, std::string& err);
+
 }  // namespace rtg

@@ -81,7 +81,7 @@ struct SceneGeom {
 };
 
 // The host-buffer queries' scratch (rtg_scene::q): one slot per kind of buffer
-enum QuerySlot { Q_RAYS, Q_HITS, Q_NORMALS, Q_RADIANCE, Q_PIXEL_IDS, Q_SURFACE, Q_COUNTS, Q_SLOTS };
+enum QuerySlot { Q_RAYS, Q_HITS, Q_NORMALS, Q_RADIANCE, Q_PIXEL_IDS, Q_SURFACE, Q_COUNTS, Q_POINTS, Q_NEAREST, Q_SLOTS };
 
 struct rtg_scene {
     int device = 0;
@@ -96,6 +96,7 @@ struct rtg_scene {
     DevBuf<rtg::DevMeshLight> mesh_lights;
     DevBuf<rtg::DevObject> objects;
     DevBuf<float4> group_box;
+    DevBuf<rtg::PointXf> point_xf;    // closest-point queries: per object (a kernel argument of its own, not in DevScene)
     DevBuf<rtg::DevMaterial> materials;
     DevBuf<rtg::DevBrdf> brdfs;
     DevBuf<rtg::DevTexture> textures;
@@ -119,6 +120,8 @@ struct rtg_scene {
     bool path_ok = false;             // path-tracing cameras may render on the wavefront path tracer
     rtg::PathState* path = nullptr;   // its buffers
     int feat = rtg::FEAT_ALL;         // scene feature bits (traversal specialisation)
+    int closest_feat = rtg::FEAT_ALL; // ... of k_closest: FEAT_XFORM too where a mesh record lacks PXF_IDENTITY
+    int closest_bad = -1;             // first sphere that is an ellipsoid (closest-point queries refuse the scene)
     int num_slots = 0;                // lights per pixel (wavefront light slots)
     int shade_sk = rtg::SK_ALL;       // shading features (k_shade variant, rtg_common.hpp SK_*)
     // wavefront buffers, grown on demand
@@ -320,6 +323,7 @@ static rtg::TableOptions table_options() {
 // The tables rtg_scene_update may write, uploaded afresh (creation, clone).
 static int upload_mutable(rtg_scene* sc, const rtg::SceneTables& T) {
     HIP_TRY(sc->objects.upload(T.objects)); HIP_TRY(sc->group_box.upload(T.group_box));
+    HIP_TRY(sc->point_xf.upload(T.point_xf));
     HIP_TRY(sc->materials.upload(T.materials)); HIP_TRY(sc->brdfs.upload(T.brdfs));
     HIP_TRY(sc->textures.upload(T.textures));
     HIP_TRY(sc->point_lights.upload(T.point_lights)); HIP_TRY(sc->area_lights.upload(T.area_lights));
@@ -348,6 +352,15 @@ static void scene_state(rtg_scene* sc, const rtg_scene_desc* d, const rtg::Scene
     sc->path_ok = T.path_ok;
     sc->max_depth = d->max_recursion_depth;
     sc->cameras.assign(d->cameras, d->cameras + d->num_cameras);
+    // k_closest's identity variants do no transform arithmetic: they are for scenes whose mesh
+    // records all carry PXF_IDENTITY (rtg_pointxf.hpp judges `transform`, feat `inv_transform`)
+    sc->closest_feat = T.feat;
+    sc->closest_bad = -1;
+    for (size_t i = 0; i < T.point_xf.size(); ++i) {
+        const int f = T.point_xf[i].flags;
+        if (d->objects[i].kind != RTG_OBJ_SPHERE && !(f & rtg::PXF_IDENTITY)) sc->closest_feat |= rtg::FEAT_XFORM;
+        if (!(f & rtg::PXF_SPHERE_OK) && sc->closest_bad < 0) sc->closest_bad = (int)i;
+    }
     const SceneGeom& g = *sc->geom;
     rtg::DevScene& S = sc->ds;
     std::memset(&S, 0, sizeof(S));
@@ -477,6 +490,7 @@ int rtg_scene_update(rtg_scene* s, const rtg_scene_desc* d, void* stream) {
         r->staged = std::move(tables[i]);
         const rtg::SceneTables& T = r->staged;
         HIP_TRY(r->objects.update(T.objects, st)); HIP_TRY(r->group_box.update(T.group_box, st));
+        HIP_TRY(r->point_xf.update(T.point_xf, st));
         HIP_TRY(r->materials.update(T.materials, st)); HIP_TRY(r->brdfs.update(T.brdfs, st));
         HIP_TRY(r->textures.update(T.textures, st));
         HIP_TRY(r->point_lights.update(T.point_lights, st)); HIP_TRY(r->area_lights.update(T.area_lights, st));
@@ -547,6 +561,7 @@ int rtg_scene_clone(const rtg_scene* src, rtg_scene** out) {
     sc->feat = src->feat; sc->shade_sk = src->shade_sk; sc->num_slots = src->num_slots;
     sc->wave_ok = src->wave_ok; sc->tree_ok = src->tree_ok; sc->path_ok = src->path_ok;
     sc->max_depth = src->max_depth;
+    sc->closest_feat = src->closest_feat; sc->closest_bad = src->closest_bad;
     // the source's DevScene over the clone's own tables (pointers where the source has entries)
     rtg::DevScene& S = sc->ds;
     S = src->ds;
@@ -1217,6 +1232,42 @@ int rtg_trace_rays_multi(rtg_scene* s, const rtg_ray* rays, int64_t n, int32_t k
     return unstage(s, bufs);
 }
 
+// ---- closest-point queries (rtg_closest.hip)
+static int closest_args(const rtg_scene* s, const void* points, int64_t n, uint32_t flags, const void* out) {
+    if (!s) return set_err(RTG_ERR_INVALID, "null scene");
+    if (n < 0 || n > INT32_MAX) return set_err(RTG_ERR_INVALID, "%lld points: at most INT32_MAX per call", (long long)n);
+    if (flags) return set_err(RTG_ERR_INVALID, "unknown query flags 0x%x", flags);
+    if (n > 0 && (!points || !out)) return set_err(RTG_ERR_INVALID, "null buffer");
+    if (s->closest_bad >= 0) {
+        std::string err;
+        const int rc = rtg::closest_unsupported(s->staged.point_xf.data(), (int)s->staged.point_xf.size(), err);
+        return set_err(rc, "%s", err.c_str());
+    }
+    return RTG_OK;
+}
+
+int rtg_closest_points_device(rtg_scene* s, const rtg_point* d_points, int64_t n, uint32_t flags, rtg_nearest* d_out,
+                              void* stream) {
+    int rc = closest_args(s, d_points, n, flags, d_out);
+    if (rc || n == 0) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(rtg::launch_closest(s->ds, s->point_xf.ptr(), s->closest_feat, d_points, (int)n, d_out, (hipStream_t)stream));
+    return RTG_OK;
+}
+
+int rtg_closest_points(rtg_scene* s, const rtg_point* points, int64_t n, uint32_t flags, rtg_nearest* out) {
+    int rc = closest_args(s, points, n, flags, out);
+    if (rc || n == 0) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t N = (size_t)n;
+    const std::initializer_list<Staged> bufs = {{Q_POINTS, N * sizeof(rtg_point), points, nullptr},
+                                                {Q_NEAREST, N * sizeof(rtg_nearest), nullptr, out}};
+    if ((rc = stage(s, bufs))) return rc;
+    HIP_TRY(rtg::launch_closest(s->ds, s->point_xf.ptr(), s->closest_feat, (rtg_point*)s->q[Q_POINTS].p, (int)n,
+                                (rtg_nearest*)s->q[Q_NEAREST].p, s->stream));
+    return unstage(s, bufs);
+}
+
 // the camera record and row range of a camera-ray batch
 static int camera_rays_args(const rtg_scene* s, const rtg_render_opts* o, const void* rays, rtg::DevCamera& C,
                             int& row_begin, int& row_end) {
@@ -1366,6 +1417,18 @@ int rtg_desc_trace_rays_multi(const rtg_scene_desc* d, const rtg_ray* rays, int6
         rc = rtg::host_trace_rays_multi(d, rays, n, k, flags, hits, counts, err);
     } catch (const std::exception& e) {
         return set_err(RTG_ERR_NOMEM, "rtg_desc_trace_rays_multi: %s", e.what());
+    }
+    return rc == RTG_OK ? RTG_OK : set_err(rc, "%s", err.c_str());
+}
+
+int rtg_desc_closest_points(const rtg_scene_desc* d, const rtg_point* points, int64_t n, uint32_t flags,
+                            rtg_nearest* out) {
+    std::string err;
+    int rc;
+    try {
+        rc = rtg::host_closest_points(d, points, n, flags, out, err);
+    } catch (const std::exception& e) {
+        return set_err(RTG_ERR_NOMEM, "rtg_desc_closest_points: %s", e.what());
     }
     return rc == RTG_OK ? RTG_OK : set_err(rc, "%s", err.c_str());
 }

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "rtg_device.hpp"
+#include "rtg_pointxf.hpp"
 #include "rtg_variants.hpp"
 #include "rtgpu.h"
 
@@ -73,6 +74,10 @@ hipError_t launch_camera_rays(const DevCamera& C, int row_begin, int row_end, in
 // ray per lane; hits: n * k records, ray-major; counts nullable (filled slots per ray).
 hipError_t launch_multihit(const DevScene& S, int feat, const rtg_ray* rays, int n, int k, rtg_hit* hits, int* counts,
                            hipStream_t stream);
+// closest-point queries (rtg_closest.hip): the nearest surface point to each of n points, one point
+// per lane; xf: the per-object placement records (rtg_pointxf.hpp), num_objects of them.
+hipError_t launch_closest(const DevScene& S, const PointXf* xf, int feat, const rtg_point* points, int n,
+                          rtg_nearest* out, hipStream_t stream);
 // surface queries (rtg_surface.hip): closest hit of n rays, one ray per lane, with the hit's shading
 // normal (normal / bump maps applied), texture coordinates, geometric normal, material and
 // GetDiffuse's coefficient; flags: RTG_QUERY_COHERENT only.  sk / feat as for launch_mega (a scene

@@ -496,7 +496,77 @@ void light_tables(const rtg_scene_desc* d, SceneTables& T) {
             T.env_mix[(size_t)e * kEnvDraws + j] = mix(((uint64_t)kRpEnv << 32) | (uint32_t)((uint32_t)e * 16384u + (uint32_t)j));
 }
 
+// The largest eigenvalue of the symmetric 3x3 matrix b (cyclic Jacobi rotations, double): a
+// fixed number of sweeps, far more than 3x3 needs to converge to the last bits.
+double sym3_max_eigen(double b[3][3]) {
+    for (int sweep = 0; sweep < 16; ++sweep)
+        for (int p = 0; p < 2; ++p)
+            for (int q = p + 1; q < 3; ++q) {
+                if (b[p][q] == 0.0) continue;
+                const double theta = (b[q][q] - b[p][p]) / (2.0 * b[p][q]);
+                const double t = (theta >= 0.0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
+                const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c;
+                for (int k = 0; k < 3; ++k) {         // columns p, q
+                    const double kp = b[k][p], kq = b[k][q];
+                    b[k][p] = c * kp - s * kq;
+                    b[k][q] = s * kp + c * kq;
+                }
+                for (int k = 0; k < 3; ++k) {         // rows p, q
+                    const double pk = b[p][k], qk = b[q][k];
+                    b[p][k] = c * pk - s * qk;
+                    b[q][k] = s * pk + c * qk;
+                }
+            }
+    return std::max(b[0][0], std::max(b[1][1], b[2][2]));
+}
+
+void point_table(const rtg_scene_desc* d, SceneTables& T) {
+    T.point_xf.resize(d->num_objects);
+    for (int i = 0; i < d->num_objects; ++i) point_xf_record(d->objects[i], T.point_xf[i]);
+}
+
 }  // namespace
+
+// rtg_pointxf.hpp.  Rows 0..2 of the 4x4 row-major matrices are their first 12 entries.
+void point_xf_record(const rtg_object& o, PointXf& X) {
+    std::memset(&X, 0, sizeof(X));
+    bool ident = true;
+    for (int k = 0; k < 12; ++k) {
+        X.fwd[k] = (float)o.transform[k];
+        X.inv[k] = (float)o.inv_transform[k];
+        ident &= o.transform[k] == ((k % 5 == 0) ? 1.0 : 0.0);
+    }
+    X.lip2 = 1.0f;
+    X.scale = 1.0f;
+    X.flags = PXF_SPHERE_OK;
+    if (ident) {
+        X.flags |= PXF_IDENTITY;
+        return;
+    }
+    // sigma_max(inv 3x3)^2: the largest eigenvalue of inv^T inv.  A NaN or an overflow ends as
+    // lip2 = inf or NaN, under which no box is skipped.
+    const double* A = o.inv_transform;
+    double b[3][3];
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) b[r][c] = A[r] * A[c] + A[4 + r] * A[4 + c] + A[8 + r] * A[8 + c];
+    const double l2 = sym3_max_eigen(b) * (1.0 + 1e-5);
+    X.lip2 = (float)l2;
+    if ((double)X.lip2 < l2) X.lip2 = std::nextafterf(X.lip2, INFINITY);
+    if (o.kind != RTG_OBJ_SPHERE) return;
+    // a sphere stays one under a similarity alone: M^T M = s^2 I within 1e-6 s^2, s = cbrt(|det M|)
+    const double* M = o.transform;
+    const double det = M[0] * (M[5] * M[10] - M[6] * M[9]) - M[1] * (M[4] * M[10] - M[6] * M[8]) +
+                       M[2] * (M[4] * M[9] - M[5] * M[8]);
+    const double s = std::cbrt(std::fabs(det)), s2 = s * s;
+    bool similar = s > 0.0 && std::isfinite(s);
+    for (int r = 0; r < 3 && similar; ++r)
+        for (int c = 0; c < 3; ++c) {
+            const double g = M[r] * M[c] + M[4 + r] * M[4 + c] + M[8 + r] * M[8 + c];
+            if (!(std::fabs(g - (r == c ? s2 : 0.0)) <= 1e-6 * s2)) similar = false;
+        }
+    X.scale = (float)s;
+    if (!similar) X.flags &= ~PXF_SPHERE_OK;
+}
 
 bool any_uv(const rtg_scene_desc* d) {
     bool uv = false;
@@ -581,6 +651,7 @@ int build_scene_tables(const rtg_scene_desc* d, const TableOptions& opt, const B
         face_tables(d, T);
     }
     const int feat = object_table(d, T);
+    point_table(d, T);
     if (opt.fast_shadow && d->num_meshes > 0)
         shadow_tables(d, opt, rb ? rb->nodes : T.nodes, rb ? rb->ext : T.node_ext, rb ? rb->tris.data() : T.tris.data(), T);
     T.ahb_split = T.ahb_mode == AHB_SPLIT && !T.anodes.empty();
@@ -663,6 +734,7 @@ int update_scene_tables(const rtg_scene_desc* d, const KeptTables& K, const Tabl
     T.mesh_begin = K.mesh_begin; T.mesh_end = K.mesh_end; T.aroot = K.aroot;
     T.ahb_mode = K.ahb_mode; T.ahb_ok = K.ahb_ok; T.ahb_split = K.ahb_split; T.bigleaf = K.bigleaf;
     const int feat = object_table(d, T);
+    point_table(d, T);
     if (!T.aroot.empty())
         for (int i = 0; i < d->num_objects; ++i)
             T.objects[i].aroot = d->objects[i].kind != RTG_OBJ_SPHERE ? T.aroot[d->objects[i].mesh] : -1;

@@ -10,6 +10,7 @@
 
 #include "rtg_ahb.hpp"
 #include "rtg_device.hpp"
+#include "rtg_pointxf.hpp"
 #include "rtgpu.h"
 
 namespace rtg {
@@ -40,6 +41,7 @@ struct SceneTables {
     std::vector<float2> face_uv;
     std::vector<DevObject> objects;
     std::vector<float4> group_box;
+    std::vector<PointXf> point_xf;      // per object: the closest-point queries' placement record (rtg_pointxf.hpp)
     std::vector<DevMaterial> materials;
     std::vector<DevBrdf> brdfs;
     std::vector<DevTexture> textures;
@@ -108,7 +110,7 @@ void keep_tables(const rtg_scene_desc* d, const SceneTables& T, KeptTables& K);
 // RTG_OK when `d` matches the signature in K, else RTG_ERR_INVALID with the first difference.
 int same_geometry(const rtg_scene_desc* d, const KeptTables& K, std::string& err);
 // The mutable tables and scalars of `d` over the geometry K was kept from: objects, group_box,
-// materials, brdfs, textures, the image records, the four analytic light arrays, env_images,
+// point_xf, materials, brdfs, textures, the image records, the four analytic light arrays, env_images,
 // env_mix, the mesh-light records, feat, shade_sk, num_slots, wave_ok, tree_ok, path_ok (and
 // mesh_begin / mesh_end / aroot / the ahb_* flags, copied from K) -- each equal, byte for byte, to
 // build_scene_tables(d)'s; every other table of T is left empty.  Reads neither d->faces, d->nodes

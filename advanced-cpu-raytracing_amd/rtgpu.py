@@ -45,6 +45,10 @@ HIT_DTYPE = np.dtype([("t", "<f4"), ("object", "<i4"), ("face", "<i4"), ("pad", 
 SURFACE_DTYPE = np.dtype([("t", "<f4"), ("object", "<i4"), ("face", "<i4"), ("material", "<i4"),
                           ("n", "<f4", (3,)), ("u", "<f4"), ("ng", "<f4", (3,)), ("v", "<f4"),
                           ("kd", "<f4", (3,)), ("pad", "<f4")])
+# rtg_point (16 B) and rtg_nearest (32 B) of the closest-point queries
+POINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("max_dist", "<f4")])
+NEAREST_DTYPE = np.dtype([("dist", "<f4"), ("object", "<i4"), ("face", "<i4"), ("pad0", "<i4"),
+                          ("p", "<f4", (3,)), ("pad1", "<f4")])
 RTG_CAMERA_SIZE = 392   # sizeof(rtg_camera), checked against the C compiler by tests/test_abi.py
 
 
@@ -178,6 +182,7 @@ EXPORTED = [
     "rtg_host_alloc", "rtg_host_free", "rtg_host_register", "rtg_host_unregister",
     "rtg_trace_rays_device", "rtg_trace_rays", "rtg_camera_rays_device", "rtg_camera_rays", "rtg_desc_trace_rays",
     "rtg_trace_rays_multi_device", "rtg_trace_rays_multi", "rtg_desc_trace_rays_multi",
+    "rtg_closest_points_device", "rtg_closest_points", "rtg_desc_closest_points",
     "rtg_radiance_rays_device", "rtg_radiance_rays",
     "rtg_surface_rays_device", "rtg_surface_rays",
     "rtg_scene_update", "rtg_scene_set_camera", "rtg_scene_num_cameras", "rtg_camera_setup",
@@ -248,6 +253,9 @@ def lib() -> ctypes.CDLL:
     L.rtg_trace_rays_multi_device.argtypes = [vp, vp, ctypes.c_int64, i32, ctypes.c_uint32, vp, vp, vp]
     L.rtg_trace_rays_multi.argtypes = [vp, vp, ctypes.c_int64, i32, ctypes.c_uint32, vp, vp]
     L.rtg_desc_trace_rays_multi.argtypes = [vp, vp, ctypes.c_int64, i32, ctypes.c_uint32, vp, vp]
+    L.rtg_closest_points_device.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_uint32, vp, vp]
+    L.rtg_closest_points.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_uint32, vp]
+    L.rtg_desc_closest_points.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_uint32, vp]
     L.rtg_radiance_rays_device.argtypes =[vp, P(RadianceOpts), vp, vp, ctypes.c_int64, vp, vp]
     L.rtg_radiance_rays.argtypes = [vp, P(RadianceOpts), vp, vp, ctypes.c_int64, vp]
     L.rtg_surface_rays_device.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_uint32, vp, vp]
@@ -304,6 +312,23 @@ def _query_multi(fn, handle, rays, k, coherent, counts):
     _check(fn(handle, rays.ctypes.data, n, k, _query_flags(False, coherent), hits.ctypes.data,
               cnt.ctypes.data if counts else None))
     return (hits, cnt) if counts else hits
+
+
+def make_points(xyz, max_dist=np.inf) -> np.ndarray:
+    """(n, 3) points (+ scalar or (n,) max_dist) -> POINT_DTYPE array."""
+    p = np.asarray(xyz, np.float32).reshape(-1, 3)
+    pts = np.zeros(len(p), POINT_DTYPE)
+    pts["x"], pts["y"], pts["z"] = p[:, 0], p[:, 1], p[:, 2]
+    pts["max_dist"] = max_dist
+    return pts
+
+
+def _query_closest(fn, handle, points):
+    """Shared body of HostScene.closest / DeviceScene.closest."""
+    points = np.ascontiguousarray(points, POINT_DTYPE)
+    out = np.zeros(points.size, NEAREST_DTYPE)
+    _check(fn(handle, points.ctypes.data, points.size, 0, out.ctypes.data))
+    return out
 
 
 def device_count() -> int:
@@ -372,6 +397,12 @@ class HostScene:
         yardstick of DeviceScene.trace_multi).  Returns the (n, k) HIT_DTYPE array, or
         (hits, counts (n,) int32) with ``counts=True``."""
         return _query_multi(lib().rtg_desc_trace_rays_multi, self.desc, rays, k, coherent, counts)
+
+    def closest(self, points):
+        """The nearest surface point to each POINT_DTYPE point on the host, no device
+        (rtg_desc_closest_points: the walk that defines the query, the yardstick of
+        DeviceScene.closest).  Returns the NEAREST_DTYPE array."""
+        return _query_closest(lib().rtg_desc_closest_points, self.desc, points)
 
     def num_cameras(self) -> int:
         n = 0
@@ -523,6 +554,19 @@ class DeviceScene:
         ray-major, optionally n int32 counts) on ``stream``; flags RTG_QUERY_COHERENT or 0."""
         _check(lib().rtg_trace_rays_multi_device(self._s, rays_ptr or None, n, k, flags, hits_ptr or None,
                                                  counts_ptr or None, stream or None))
+
+    def closest(self, points):
+        """The nearest point of the scene's surface to each POINT_DTYPE point (make_points), on host
+        arrays (rtg_closest_points; synchronous): a NEAREST_DTYPE array with the world-space
+        distance, the object and global face (-1: a sphere) and the closest point ``p``.  Nothing
+        strictly nearer than ``max_dist``, or a point that is not finite: dist = max_dist,
+        object = face = -1, p = 0."""
+        return _query_closest(lib().rtg_closest_points, self._s, points)
+
+    def closest_device(self, points_ptr: int, n: int, out_ptr: int, stream: int = 0):
+        """Asynchronous closest-point queries on device buffers (n x 16 B points, n x 32 B results)
+        on ``stream`` (rtg_closest_points_device)."""
+        _check(lib().rtg_closest_points_device(self._s, points_ptr or None, n, 0, out_ptr or None, stream or None))
 
     def camera_rays(self, camera: int = 0, rows=(0, 0), sample: int = 0, seed: int = 0x5EED) -> np.ndarray:
         """The rays render() traces for ``camera`` at sample index ``sample`` and ``seed``, rows

@@ -531,6 +531,72 @@ int rtg_desc_trace_rays_multi(const rtg_scene_desc* desc, const rtg_ray* rays, i
                               rtg_hit* hits, int32_t* counts);
 
 /* ------------------------------------------------------------------------- */
+/* Closest-point queries: the nearest point of the scene's surface to a       */
+/* point, its distance, and the object and face it lies on.  No ray in it:    */
+/* the same BVH, pruned by distance to a box.  Added symbols only --          */
+/* RTG_ABI_VERSION stays 6.                                                   */
+/* ------------------------------------------------------------------------- */
+typedef struct { float x, y, z, max_dist; } rtg_point;        /* 16 B; max_dist = INFINITY: unbounded */
+typedef struct { float dist; int32_t object, face, pad0;       /* 32 B: two 16-byte stores            */
+                 float px, py, pz, pad1; } rtg_nearest;
+
+/* Semantics (the host walk of rtg_desc_closest_points defines them; the device repeats its
+ * decisions with the same float arithmetic in the same order, so the two agree bit for bit):
+ *  - Result: dist is the world-space distance, object the object index, face the global face
+ *    index (-1 for a sphere), (px, py, pz) the world-space closest point; pad0 = pad1 = 0.
+ *    Miss -- nothing strictly nearer than |max_dist|, or a coordinate of the point not finite:
+ *    dist = max_dist (its own bits), object = face = -1, the point zeros.
+ *  - Candidates are compared on the squared distance d2.  A candidate (d2, object, face) replaces
+ *    the held one iff d2 < best_d2, or d2 == best_d2 and (object, face) is lexicographically
+ *    smaller.  best_d2 starts at max_dist * max_dist with nothing held; while nothing is held only
+ *    d2 < best_d2 accepts.  A NaN d2 is never accepted.  dist = sqrtf(best_d2).  Only the square of
+ *    max_dist enters: its sign is ignored (-3 admits what 3 admits, and a miss still reports
+ *    max_dist's own bits, -3); max_dist = 0 or NaN admits nothing.
+ *  - Every object counts, RTG_OBJF_SHADOW_SKIP meshes included.  Motion blur is ignored: objects
+ *    stand where they are at time 0.
+ *  - Meshes: the point-to-triangle test is the region-based one (Ericson, Real-Time Collision
+ *    Detection 5.1.5) on the walk's face record a = v0, ab = -(v0 - v1), ac = -(v0 - v2), the
+ *    regions tested in the order A, B, AB, C, AC, BC, interior; the closest point is
+ *    a + ab v + ac w.  On well-shaped triangles dist is within a few ulp of the largest coordinate
+ *    involved; on slivers the cross terms cancel and the error can be a thousand times that, so
+ *    what is promised there is device == host, not a tolerance.  A zero-area face contributes
+ *    whatever the region tests give it (possibly nothing: a NaN d2).
+ *  - The walk, per mesh object, over the (base) mesh's BVH: first a descent from the root to one
+ *    leaf, at each inner node towards the child whose box is nearer (a tie goes left), whose faces
+ *    seed the bound; then the pre-order walk, a node skipped iff the squared distance from the
+ *    point to its box exceeds best_d2 * lip2.  There is no object-level box test.
+ *  - Transforms: an object whose transform is exactly the identity does no transform arithmetic
+ *    (lip2 = 1).  Otherwise boxes are tested against the local point inv_transform * p, with
+ *    lip2 = sigma_max(inv_transform 3x3)^2 * (1 + 1e-5) (a local displacement is at most sigma_max
+ *    times the world one), and every visited face is carried to world space by `transform` and
+ *    tested there against the world point: leaves are exact in world space.  Both matrices are
+ *    narrowed to float first.
+ *  - Spheres: d = |length(p - centre) - radius|, the closest point centre + (p - centre) * (radius /
+ *    length), or centre + (radius, 0, 0) at the centre itself.  A sphere under a similarity
+ *    (transform^T transform within 1e-6 s^2 of s^2 I, s = cbrt(|det|)) is the sphere of world
+ *    centre transform * centre and radius radius * s.  Any other transform makes an ellipsoid, whose
+ *    closest point is iterative: such a scene is refused by all three entry points with
+ *    RTG_ERR_UNSUPPORTED and a message naming the object; no buffer is touched.
+ *  - flags must be 0 (any bit: RTG_ERR_INVALID).  n in [0, INT32_MAX]; n == 0 is RTG_OK and touches
+ *    no buffer.  A null scene, or a null buffer with n > 0, is RTG_ERR_INVALID.  The refusal of
+ *    an ellipsoid scene comes before the n == 0 rule: such a scene answers RTG_ERR_UNSUPPORTED for
+ *    every n, 0 included (the argument errors above come before both).
+ *  - Out of scope: the sign of the distance, the k nearest primitives, ellipsoids, a motion-blur
+ *    time, a packet walk. */
+
+/* Device-resident buffers on `stream`; asynchronous, allocates nothing and touches no render
+ * state.  A multi-device scene answers on its first replica.  Works on clones and after
+ * rtg_scene_update (the placement records are updated with the objects). */
+int rtg_closest_points_device(rtg_scene* scene, const rtg_point* d_points, int64_t n, uint32_t flags,
+                              rtg_nearest* d_out, void* stream);
+/* Same on host buffers (synchronous; the scene's query scratch and its own stream). */
+int rtg_closest_points(rtg_scene* scene, const rtg_point* points, int64_t n, uint32_t flags, rtg_nearest* out);
+/* Host only, no device: the walk that defines the query -- the yardstick of the device query, bit
+ * for bit.  RTG_ERR_INVALID for a description without nodes (RTG_LOAD_DEVICE_BVH). */
+int rtg_desc_closest_points(const rtg_scene_desc* desc, const rtg_point* points, int64_t n, uint32_t flags,
+                            rtg_nearest* out);
+
+/* ------------------------------------------------------------------------- */
 /* Surface queries: what the renderer knows about the point a ray hits --     */
 /* shading normal, texture coordinates, material and diffuse coefficient.     */
 /* Added symbols and one type only -- RTG_ABI_VERSION stays 6.                */

@@ -13,7 +13,7 @@ renders: RTG_FRAME_KERNEL=0 splits the sample pass into k_primary + k_shade_shad
 RTG_RENDER_EXACT_SHADOW gives k_shadow with the reference walk).  k_primary is the yardstick of
 (a): the same walk on the same rays, with a 32-byte ray read in place of ray generation.
 
-    python tools/query_bench.py [--launches 50] [--reps 3] [--out FILE] [--sections query,radiance,surface,update,multi]
+    python tools/query_bench.py [--launches 50] [--reps 3] [--out FILE] [--sections query,radiance,surface,update,multi,closest]
 
 The radiance section (rtg_radiance_rays_device, DeviceScene.radiance_device) runs on the same
 height field and on the path-tracing fixture tests/golden/scenes/pt_cornell.xml at its own size:
@@ -45,6 +45,17 @@ The multi section (rtg_trace_rays_multi_device, DeviceScene.trace_multi_device) 
 height field: the k nearest hits for k = 1, 2, 4, 8 on the camera's rays in pixel order and on the
 same rays randomly permuted, with trace_device (closest hit, no hint) on the same rays in the same
 session beside them.
+
+The closest section (rtg_closest_points_device, DeviceScene.closest_device) runs on the same height
+field, about two million points a launch, in Gpoints/s:
+
+  (g)  a jittered 512 x 512 x 8 grid through the box of the camera's hit points (its height that
+       of the field plus a twentieth of its width), in grid order    (g-perm) the same, shuffled
+  (h)  the camera rays' hit points lifted along the shading normal by 1e-3 to 1 (log-uniform)
+
+each with max_dist = inf and with a radius of four mean cell sizes.  A 65 536-point sample of every
+case is checked against the host walk bit for bit before anything is timed.  The library is the
+one rtgpu loads ($RTGPU_LIB for an experiment's build, as in the seed-pass comparison of DESIGN.md).
 """
 import argparse
 import os
@@ -440,6 +451,84 @@ def multi_main(args):
     return lines
 
 
+def closest_main(args):
+    """Closest-point queries (rtg_closest_points_device) on the headline height field: lines of text."""
+    import torch
+
+    import rtgpu
+    import scenes
+
+    tmp = tempfile.mkdtemp(prefix="query_bench_")
+    xml = scenes.synthetic_heightfield(tmp, K=args.K, width=args.width, height=args.height)
+    os.chdir(tmp)
+    hs = rtgpu.HostScene(xml)
+    ds = rtgpu.DeviceScene(hs, 0)
+    rng = np.random.default_rng(1234)
+    rays = ds.camera_rays()
+    hits, nrm = ds.trace(rays, normals=True)
+    ok = hits["object"] >= 0
+    o = np.stack([rays["ox"], rays["oy"], rays["oz"]], 1)[ok]
+    d = np.stack([rays["dx"], rays["dy"], rays["dz"]], 1)[ok]
+    hit_xyz = o + d * hits["t"][ok][:, None]
+    lo, hi = hit_xyz.min(0).astype(np.float64), hit_xyz.max(0).astype(np.float64)
+    hi[2] += 0.05 * (hi[0] - lo[0])
+    gx, gy, gz = 512, 512, 8
+    cell = (hi - lo) / (gx, gy, gz)
+    zz, yy, xx = np.meshgrid(np.arange(gz), np.arange(gy), np.arange(gx), indexing="ij")
+    grid = np.stack([xx, yy, zz], -1).reshape(-1, 3)
+    grid = (lo + (grid + rng.random(grid.shape)) * cell).astype(np.float32)
+    lifted = (hit_xyz + nrm[ok, :3] * (10.0 ** rng.uniform(-3.0, 0.0, (len(hit_xyz), 1)))).astype(np.float32)
+    radius = float(4.0 * np.sqrt((hi[0] - lo[0]) * (hi[1] - lo[1]) / (args.K / 2)))
+    sets = {"(g) grid order": grid, "(g-perm) shuffled": grid[rng.permutation(len(grid))], "(h) lifted hit points": lifted}
+    dev = torch.device("cuda:0")
+    st = torch.cuda.current_stream().cuda_stream
+    cases, bufs, held = [], {}, {}
+    for which, xyz in sets.items():
+        for label, md in (("max_dist = inf", np.inf), ("max_dist = %.4g" % radius, radius)):
+            pts = rtgpu.make_points(xyz, md)
+            key = f"{which}, {label}"
+            d_pts = torch.from_numpy(pts.view(np.float32).reshape(-1, 4).copy()).to(dev)
+            d_out = torch.empty((len(pts), 8), dtype=torch.int32, device=dev)
+            ds.closest_device(d_pts.data_ptr(), len(pts), d_out.data_ptr(), stream=st)
+            torch.cuda.synchronize()
+            got = d_out.cpu().numpy()
+            pick = rng.choice(len(pts), 65536, replace=False)
+            want = hs.closest(pts[pick])
+            assert got[pick].tobytes() == want.tobytes(), (key, "device != host walk")
+            held[key] = float((got[:, 1] >= 0).mean())
+            bufs[key] = (d_pts, d_out, len(pts))
+            cases.append(key)
+
+    def run(key, reps):
+        d_pts, d_out, n = bufs[key]
+        for _ in range(reps):
+            ds.closest_device(d_pts.data_ptr(), n, d_out.data_ptr(), stream=st)
+
+    for key in cases:
+        run(key, args.warmup)
+    torch.cuda.synchronize()
+    ms = {key: [] for key in cases}
+    for _ in range(args.reps):
+        for key in cases:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            run(key, args.launches)
+            e1.record()
+            e1.synchronize()
+            ms[key].append(e0.elapsed_time(e1) / args.launches)
+    lines = [f"closest: synthetic_heightfield K={args.K}, {args.launches} launches x {args.reps} interleaved repetitions, "
+             f"device {torch.cuda.get_device_name(0)}, library {os.path.basename(rtgpu.LIB_PATH)} (65 536 points of every "
+             f"case equal the host walk bit for bit)",
+             f"{'case':48s} {'points':>9s} {'ms (median)':>12s} {'min':>8s} {'max':>8s} {'Gpoints/s':>10s} {'answered':>9s}"]
+    for key in cases:
+        v, n = ms[key], bufs[key][2]
+        lines.append(f"{key:48s} {n:9d} {np.median(v):12.4f} {min(v):8.4f} {max(v):8.4f} {n / np.median(v) / 1e6:10.3f} "
+                     f"{held[key]:9.3f}")
+    spread = lambda v: (max(v) - min(v)) / np.median(v) * 100
+    lines.append("spread over the repetitions: " + ", ".join(f"{spread(ms[key]):.1f} %" for key in cases))
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--setups", type=int, default=9, help="update section: calls per set-up time")
@@ -465,6 +554,8 @@ def main():
         text += update_main(args)
     if "multi" in sections:
         text += multi_main(args)
+    if "closest" in sections:
+        text += closest_main(args)
     text = "\n".join(text)
     print(text)
     if out:
