@@ -565,6 +565,20 @@ DEV void sload_rec(const float4* p, rtg_s8& a, rtg_s4& b) {      // 48 B: a face
 DEV void sload_node(const float4* p, rtg_s8& a) {                // 32 B: a reference BVH node
     asm volatile("s_load_dwordx8 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=&s"(a) : "s"(uniform_ptr(p)) : "memory");
 }
+// The same records at base + a 32-bit byte offset held in an SGPR (rec_off below): the load adds
+// the two itself, zero-extending the offset as rec_at does, and the address's s_add_u32 /
+// s_addc_u32 pair goes (walk_bvh_packet_lx, walk_wide_any_pk).
+DEV void sload_wnode(const WNode* base, uint32_t off, rtg_s16& a, rtg_s16& b) {
+    asm volatile("s_load_dwordx16 %0, %2, %3\n\ts_load_dwordx16 %1, %2, %3 offset:0x40\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&s"(a), "=&s"(b) : "s"(uniform_ptr(base)), "s"(off) : "memory");
+}
+DEV void sload_rec(const float4* base, uint32_t off, rtg_s8& a, rtg_s4& b) {
+    asm volatile("s_load_dwordx8 %0, %2, %3\n\ts_load_dwordx4 %1, %2, %3 offset:0x20\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&s"(a), "=&s"(b) : "s"(uniform_ptr(base)), "s"(off) : "memory");
+}
+DEV void sload_node(const float4* base, uint32_t off, rtg_s8& a) {
+    asm volatile("s_load_dwordx8 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=&s"(a) : "s"(uniform_ptr(base)), "s"(off) : "memory");
+}
 DEV float4 f4(int x, int y, int z, int w) {
     return make_float4(__int_as_float(x), __int_as_float(y), __int_as_float(z), __int_as_float(w));
 }
@@ -880,6 +894,10 @@ constexpr int kDeferLeaf = 16;
 template <int BYTES, typename T>
 DEV const T* rec_at(const T* base, int i) {
     return (const T*)((const char*)base + (uint32_t)i * (uint32_t)BYTES);
+}
+template <int BYTES>
+DEV uint32_t rec_off(int i) {
+    return (uint32_t)i * (uint32_t)BYTES;
 }
 #ifndef RTG_DEFER_LANES
 #define RTG_DEFER_LANES 16
@@ -1367,81 +1385,89 @@ DEV bool walk_bvh_packet_lx(const DevScene& S, int begin, int end, const Ray& r,
     const float slack0 = slab_slack0(sf, q.fast);
     const float kc = (q.fast & sc.ok) ? 1.0f + 0x1p-20f : __builtin_nanf("");
     float minTc = minT * kc;                         // follows minT: renewed after a leaf's faces
-    int i = begin;                                   // wave-uniform
-    while (i < end) {
-        i = __builtin_amdgcn_readfirstlane(i);
-        const int ip1 = i + 1;
+    int i = begin;                                   // wave-uniform: begin, i + 1 or a record's skip word
+    if (i >= end) return false;
+    // The step's scalar side (profiles/r16_node_loops_isa_blocks.txt).  An inner
+    // node costs 7 SALU and 4 branches around its 22 VALU: the offset's shift, i + 1, the record's load
+    // (base + offset in the instruction), the leaf word's test, the NaN lanes' vote, the ballot's
+    // compare and one select between i + 1 and skip, the second leaf test, the loop test at the foot.
+    //  - The inner step and the leaf step are two if-thens in a row, not an if / else: the loop holds
+    //    divergent branches (box_hit, the face test's fallback), so its control flow is structurized,
+    //    and an if / else of uniform conditions comes out of that with a flag set, tested and branched
+    //    on in blocks of their own.  The empty asm on `leaf` keeps the compiler from threading the two
+    //    tests into an if / else again.
+    //  - nx starts as the record's skip word and the select writes it in place, so the leaf path needs
+    //    no move and the loop test reads one register on both paths.
+    //  - i + 1 is made before the load (an asm statement: the compiler would sink it below), which
+    //    lets the load's result overwrite i's register: no copy of nx into i at the foot, and the loop
+    //    test falls through into the next step.  The LEAF_EXT leaf recovers its index as ip1 - 1.
+    do {
         rtg_s8 nd;
-        sload_node(rec_at<32>(S.nodes, i), nd);
+        const uint32_t off = rec_off<32>(i);
+        int ip1;
+        asm("s_add_i32 %0, %1, 1" : "=s"(ip1) : "s"(i) : "scc");
+        sload_node(S.nodes, off, nd);
         const float4 a = f4(nd[0], nd[1], nd[2], nd[3]), b = f4(nd[4], nd[5], nd[6], nd[7]);
-        const int skip = nd[6], leaf = nd[7];
-        float pv;                                    // > 0: the lane passes
+        int nx = nd[6], leaf = nd[7];                // nx: where the walk goes next, the skip link unless a lane passes an inner node
         if (leaf < 0) {
-            pv = slab_cons_pk(a.x, a.y, a.z, a.w, b.x, b.y, sc, minTc);
+            float pv = slab_cons_pk(a.x, a.y, a.z, a.w, b.x, b.y, sc, minTc);   // > 0: the lane passes
             if (__builtin_expect(__ballot(pv != pv) != 0, 0)) {
                 if (pv != pv) pv = box_hit(a.x, a.y, a.z, a.w, b.x, b.y, r, minT) ? 1.0f : -1.0f;
             }
-        } else {
-            // the exact decision at the lane's own minT (slack0 = inf off the fast path: box_hit)
-            pv = box_pass_v(a.x, a.y, a.z, a.w, b.x, b.y, r, sf, minT, INFINITY, slack0);
-        }
-        bool pass = pv > 0.0f;
-        // (the next node and the leaf to test: walk_bvh_packet's five scalar instructions)
-        const int cur = i;
-        int lf;
-        {
-            const uint64_t pm = __builtin_amdgcn_ballot_w64(pass);
-            int nx;
+            const uint64_t pm = __builtin_amdgcn_ballot_w64(pv > 0.0f);
             asm("s_cmp_lg_u64 %[pm], 0\n\t"
-                "s_cselect_b32 %[lf], %[leaf], 0\n\t"
-                "s_cmp_lt_i32 %[lf], 0\n\t"
-                "s_cselect_b32 %[nx], %[ip1], %[skip]"
-                : [lf] "=&s"(lf), [nx] "=&s"(nx)
-                : [pm] "s"(pm), [leaf] "s"(leaf), [ip1] "s"(ip1), [skip] "s"(skip)
+                "s_cselect_b32 %[nx], %[ip1], %[nx]"
+                : [nx] "+s"(nx)
+                : [pm] "s"(pm), [ip1] "s"(ip1)
                 : "scc");
-            i = nx;
         }
-        if (lf > 0) {
-            int first = leaf >> 8, cnt = leaf & 255;
-            if (leaf == LEAF_EXT) {
-                const int2 e = S.node_ext[cur];
-                first = __builtin_amdgcn_readfirstlane(e.x);
-                cnt = __builtin_amdgcn_readfirstlane(e.y);
-            }
-            if constexpr (DEFER) {
-                const uint64_t m = __ballot(pass);
-                if (cnt > kDeferLeaf && __popcll(m) <= RTG_DEFER_LANES) {
-                    // one atomic per wave for the lanes that reached the leaf
-                    const int lane = threadIdx.x & 63, lead = __ffsll((long long)m) - 1;
-                    int base = 0;
-                    if (lane == lead) base = atomicAdd(dc->count, __popcll(m));
-                    base = __shfl(base, lead);
-                    const int slot = base + __popcll(m & ((1ull << lane) - 1ull));
-                    if (pass && slot < dc->cap) {
-                        float4* qe = dc->e + 3 * (size_t)slot;
-                        qe[0] = make_float4(r.o.x, r.o.y, r.o.z, minT);
-                        qe[1] = make_float4(r.d.x, r.d.y, r.d.z, __int_as_float(dc->ray));
-                        qe[2] = make_float4(__int_as_float(first), __int_as_float(cnt), __int_as_float(k), 0.f);
-                        dc->deferred = true;
-                        pass = false;                // queued: no test here, minT unchanged
-                    }
-                    // (a lane whose entry did not fit tests the leaf below)
+        asm("" : "+s"(leaf));
+        if (leaf >= 0) {
+            // the exact decision at the lane's own minT (slack0 = inf off the fast path: box_hit)
+            bool pass = box_pass_v(a.x, a.y, a.z, a.w, b.x, b.y, r, sf, minT, INFINITY, slack0) > 0.0f;
+            if (__ballot(pass)) {                    // (a leaf nobody reaches costs no face test)
+                int first = leaf >> 8, cnt = leaf & 255;
+                if (leaf == LEAF_EXT) {
+                    const int2 e = S.node_ext[ip1 - 1];
+                    first = __builtin_amdgcn_readfirstlane(e.x);
+                    cnt = __builtin_amdgcn_readfirstlane(e.y);
                 }
+                if constexpr (DEFER) {
+                    const uint64_t m = __ballot(pass);
+                    if (cnt > kDeferLeaf && __popcll(m) <= RTG_DEFER_LANES) {
+                        // one atomic per wave for the lanes that reached the leaf
+                        const int lane = threadIdx.x & 63, lead = __ffsll((long long)m) - 1;
+                        int base = 0;
+                        if (lane == lead) base = atomicAdd(dc->count, __popcll(m));
+                        base = __shfl(base, lead);
+                        const int slot = base + __popcll(m & ((1ull << lane) - 1ull));
+                        if (pass && slot < dc->cap) {
+                            float4* qe = dc->e + 3 * (size_t)slot;
+                            qe[0] = make_float4(r.o.x, r.o.y, r.o.z, minT);
+                            qe[1] = make_float4(r.d.x, r.d.y, r.d.z, __int_as_float(dc->ray));
+                            qe[2] = make_float4(__int_as_float(first), __int_as_float(cnt), __int_as_float(k), 0.f);
+                            dc->deferred = true;
+                            pass = false;                // queued: no test here, minT unchanged
+                        }
+                        // (a lane whose entry did not fit tests the leaf below)
+                    }
+                }
+                for (int f = first; f < first + cnt; ++f) {
+                    rtg_s8 ra;
+                    rtg_s4 rb;
+                    sload_rec(S.tris, rec_off<48>(f), ra, rb);
+                    const float4 R[3] = {f4(ra[0], ra[1], ra[2], ra[3]), f4(ra[4], ra[5], ra[6], ra[7]),
+                                         f4(rb[0], rb[1], rb[2], rb[3])};
+                    float t;
+                    const bool ok = tri_test_pk(R, r, minT, t, pass ? 1.0f : -1.0f) > 0.0f;
+                    minT = ok ? t : minT;
+                    hitFace = ok ? f : hitFace;
+                }
+                minTc = minT * kc;
             }
-            for (int f = first; f < first + cnt; ++f) {
-                rtg_s8 ra;
-                rtg_s4 rb;
-                sload_rec(rec_at<48>(S.tris, f), ra, rb);
-                const float4 R[3] = {f4(ra[0], ra[1], ra[2], ra[3]), f4(ra[4], ra[5], ra[6], ra[7]),
-                                     f4(rb[0], rb[1], rb[2], rb[3])};
-                float t;
-                const bool ok = tri_test_pk(R, r, minT, t, pass ? 1.0f : -1.0f) > 0.0f;
-                minT = ok ? t : minT;
-                hitFace = ok ? f : hitFace;
-            }
-            minTc = minT * kc;
         }
-    }
+        i = nx;
+    } while (i < end);
     return hitFace != face0;
 }
 
@@ -1470,7 +1496,7 @@ DEV int walk_wide_any_pk(const DevScene& S, int node, const Ray& lr, float minT0
         }
         node = __builtin_amdgcn_readfirstlane(node);
         rtg_s16 na, nb;
-        sload_wnode(rec_at<128>(S.anodes, node), na, nb);
+        sload_wnode(S.anodes, rec_off<128>(node), na, nb);
         if (livef > 0.0f) c.wnode();
         float tn[4], hv[4];
 #pragma unroll
@@ -1527,7 +1553,7 @@ DEV int walk_wide_any_pk(const DevScene& S, int node, const Ray& lr, float minT0
             for (int e = first; e < first + cnt; ++e) {
                 rtg_s8 ra;
                 rtg_s4 rb;
-                sload_rec(rec_at<48>(S.ahtris, e), ra, rb);
+                sload_rec(S.ahtris, rec_off<48>(e), ra, rb);
                 if (hk > 0.0f) c.template tri<true>();
                 const float4 R[3] = {f4(ra[0], ra[1], ra[2], ra[3]), f4(ra[4], ra[5], ra[6], ra[7]), f4(rb[0], rb[1], rb[2], rb[3])};
                 float t;
@@ -1536,7 +1562,7 @@ DEV int walk_wide_any_pk(const DevScene& S, int node, const Ray& lr, float minT0
                 // the exact decisions on the face's reference leaf box: reachable at minT0
                 // (necessary), and at limit (sufficient, for an instance whose world box passes)
                 rtg_s8 rn;
-                sload_node(rec_at<32>(S.nodes, ra[3]), rn);
+                sload_node(S.nodes, rec_off<32>(ra[3]), rn);
                 // (few faces get here: the exact decisions' constants are made on the spot, from a
                 // laundered origin so that they are not hoisted into the walk's registers -- hoisted,
                 // k_frame's scratch is 28 B per lane against 8; a lane with okv > 0 walks, so it is

@@ -2,7 +2,10 @@
 loops: SALU / VALU / SMEM / VMEM / branch counts per block, with the loop depth the compiler
 annotates), for comparing code shapes of a kernel between builds on the CPU.
 
-    python tools/isa_blocks.py listing.s <kernel-name-regex>"""
+    python tools/isa_blocks.py listing.s <kernel-name-regex> [--min-depth N]
+
+--min-depth N prints only the blocks inside loops of depth N or more (1: every block of the walks'
+node and face loops, without the straight-line code around them); the totals stay the kernel's."""
 import argparse
 import re
 
@@ -45,6 +48,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("listing")
     ap.add_argument("kernel")
+    ap.add_argument("--min-depth", type=int, default=0)
     a = ap.parse_args()
     name, body = kernel_body(a.listing, a.kernel)
     print(name)
@@ -70,6 +74,8 @@ def main():
         for k, v in n.items():
             tot[k] = tot.get(k, 0) + v
         depth = re.findall(r"Depth=(\d)", b["note"])
+        if int(max(depth) if depth else 0) < a.min_depth:
+            continue
         print(f"{b['name']:12s} d{max(depth) if depth else 0} " +
               " ".join(f"{k}={n.get(k, 0)}" for k in ("salu", "valu", "smem", "vmem", "lds", "branch")) +
               (f" scratch={n['scratch']}" if n.get("scratch") else ""))
