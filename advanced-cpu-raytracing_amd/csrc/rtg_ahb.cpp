@@ -1,7 +1,7 @@
 // Any-hit BVH for shadow rays (rtg_ahb.hpp): host build.
 //
 // CastShadowRay (raytracer.cpp:585-623) answers a boolean, so its traversal structure is free;
-// what must stay the reference's are the decisions (rtg_common.hpp walk_wide_any): a face f of
+// what must stay the reference's are the decisions (rtg_anyhit.hpp walk_wide_any_pk): a face f of
 // reference leaf L decides "shadow" when IntersectFace accepts it below the light distance and
 // L's box B_L passes the slab test at that distance, and only a face that IntersectFace accepts
 // and whose B_L passes at the initial minT can matter at all.  The tree below is therefore

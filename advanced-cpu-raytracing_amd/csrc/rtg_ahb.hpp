@@ -1,4 +1,4 @@
-// Any-hit BVH for shadow rays (host build; device walk: rtg_common.hpp walk_wide_any).
+// Any-hit BVH for shadow rays (host build; device walk: rtg_anyhit.hpp walk_wide_any_pk).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -123,7 +123,7 @@ struct rtg_scene {
     int closest_feat = rtg::FEAT_ALL; // ... of k_closest: FEAT_XFORM too where a mesh record lacks PXF_IDENTITY
     int closest_bad = -1;             // first sphere that is an ellipsoid (closest-point queries refuse the scene)
     int num_slots = 0;                // lights per pixel (wavefront light slots)
-    int shade_sk = rtg::SK_ALL;       // shading features (k_shade variant, rtg_common.hpp SK_*)
+    int shade_sk = rtg::SK_ALL;       // shading features (k_shade variant, rtg_device.hpp SK_*)
     // wavefront buffers, grown on demand
     WaveWork work;
     // scratch for the host-buffer entry point (both of the same pixel count)
@@ -608,7 +608,7 @@ void rtg_scene_destroy(rtg_scene* s) {
     delete s;
 }
 
-// Band k of part `part` of `parts` (rtgpu.h RTG_PART_BAND_ROWS; part_row in rtg_common.hpp):
+// Band k of part `part` of `parts` (rtgpu.h RTG_PART_BAND_ROWS; part_row in rtg_frame.hpp):
 // round-robin, rotated by one slot per round of `parts` bands.  Increasing in k.
 static int part_band(int part, int parts, int k) {
     int slot = (part - k) % parts;
@@ -729,7 +729,7 @@ static int prepare(rtg_scene* s, const rtg_render_opts* o, rtg::DevCamera& C, rt
     P.part_index = o->part_index;
     if (P.part_index < 0 || P.part_index >= P.part_count)
         return set_err(RTG_ERR_INVALID, "part %d of %d", P.part_index, P.part_count);
-    // this part's bands of RTG_PART_BAND_ROWS rows (part_row in rtg_common.hpp) and its row
+    // this part's bands of RTG_PART_BAND_ROWS rows (part_row in rtg_frame.hpp) and its row
     // count; tiles of 16 compact rows (two bands; a wave's 8 rows are one band)
     static_assert(RTG_PART_BAND_ROWS == 8, "part_row's band shift");
     const int bands = (P.row_end - P.row_begin + RTG_PART_BAND_ROWS - 1) / RTG_PART_BAND_ROWS;

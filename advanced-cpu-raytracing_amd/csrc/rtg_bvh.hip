@@ -30,7 +30,7 @@
 #include <type_traits>
 #include <vector>
 
-#include "rtg_common.hpp"
+#include "rtg_isect.hpp"
 #include "rtg_devmem.hpp"
 #include "rtg_kernels.hpp"
 

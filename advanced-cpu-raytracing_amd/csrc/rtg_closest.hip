@@ -14,7 +14,7 @@
 // ones (LEAF_EXT) too: a point's nearest faces are few, and the candidate rule needs no order.
 // Placement comes from the PointXf side table (rtg_pointxf.hpp), an argument of its own:
 // DevScene and DevObject are the ray walks' and stay as they are.  No LDS, no atomics.
-#include "rtg_common.hpp"
+#include "rtg_isect.hpp"
 #include "rtg_kernels.hpp"
 
 namespace rtg {

@@ -19,6 +19,7 @@
 // range.  Objects, materials, BRDFs, lights, textures are small tables.
 #pragma once
 
+#include <hip/hip_runtime.h>
 #include <stdint.h>
 
 namespace rtg {
@@ -58,12 +59,9 @@ enum : int { WCHILD_EMPTY = -1 };
 // reference walk (its secondary rays are incoherent: the packet walk measured slower on C5).
 // (Rejected shadow walks, removed in round 6: the reference walk as wave packets, an any-hit
 // climb from the ray's origin leaf, round 2's collapsed tree on compressed 64-B nodes.)
-// Camera rays: RTG_PRIMARY_PACKET -- 2 (default): the reference walk as wave
-// packets with scalar-cache records and select face tests (k_primary 0.227 -> 0.205 ms on the
-// headline, profiles/r04c_packet_ab.txt); 1: round 2's packet form; 0: per lane.  DESIGN.md §5.
-#ifndef RTG_PRIMARY_PACKET
-#define RTG_PRIMARY_PACKET 2
-#endif
+// Camera rays of scenes without large leaves walk the reference BVH as wave packets with
+// scalar-cache records and select face tests (rtg_walk.hpp walk_bvh_packet; k_primary 0.227 ->
+// 0.205 ms on the headline, profiles/r04c_packet_ab.txt).
 
 struct DevMaterial {
     int type, brdf, pad0, pad1;
@@ -131,7 +129,7 @@ enum : int { SK_TEX = 1, SK_BRDF = 2, SK_XLIGHT = 4, SK_ALL = 7 };
 constexpr int kCoopLeaf = RTG_COOP_LEAF;
 constexpr int kBigLeaf = 8;
 
-// env_direction's table of inner RNG hashes (rtg_common.hpp): three draws per candidate, 4 096
+// env_direction's table of inner RNG hashes (rtg_shade.hpp): three draws per candidate, 4 096
 // candidates per environment light, purpose RP_ENV
 constexpr int kEnvDraws = 3 * 4096;
 constexpr uint32_t kRpEnv = 5;
@@ -172,7 +170,7 @@ struct DevScene {
     int exact_shadow;                  // RTG_RENDER_EXACT_SHADOW: shadow rays take the reference walk
     int ahb_split;                     // the any-hit tree splits large leaves (AHB_SPLIT)
     int ordered;                       // RTG_RENDER_ORDERED (plain mesh scenes with an any-hit tree)
-    // RTG_GUARD builds (fault hunting): table sizes and a violation bit mask (rtg_common.hpp GIDX)
+    // RTG_GUARD builds (fault hunting): table sizes and a violation bit mask (rtg_math.hpp GIDX)
     int* guard;
     int num_faces, num_textures, num_images, num_materials;
 };

@@ -5,7 +5,7 @@
 // the general instantiation (rtg_mega.hip; the rule: rtg_variants.hpp mega_variant).  Same
 // code, same results: the feature bits only drop code the scene cannot reach.
 
-// the fused kernels keep trav_ray's ray unlaundered (rtg_common.hpp: laundering it costs C2
+// the fused kernels keep trav_ray's ray unlaundered (rtg_walk.hpp: laundering it costs C2
 // 6 %, profiles/r05ag_sphere_launder_ab.txt)
 #define RTG_XFORM_LAUNDER 0
 #include "rtg_kernels.hpp"

@@ -3,7 +3,7 @@
 // scenes (BRDF shading, point / area / directional lights, meshes and spheres) below the
 // ray-tree pipeline's frame size.  Same code, same results.
 
-// the fused kernels keep trav_ray's ray unlaundered (rtg_common.hpp: laundering it costs C2
+// the fused kernels keep trav_ray's ray unlaundered (rtg_walk.hpp: laundering it costs C2
 // 6 %, profiles/r05ag_sphere_launder_ab.txt)
 #define RTG_XFORM_LAUNDER 0
 #include "rtg_kernels.hpp"

@@ -12,7 +12,7 @@
 // the device decides as the host walk (host_query.cpp multi_one) does.  Leaves are always tested
 // in order by their own lane, large ones (LEAF_EXT) too: the cooperative leaf reduction of
 // walk_bvh keeps one survivor per leaf, and a hit list needs every accepted face in leaf order.
-#include "rtg_common.hpp"
+#include "rtg_walk.hpp"
 #include "rtg_kernels.hpp"
 
 namespace rtg {
@@ -67,17 +67,16 @@ DEV float list_insert(HitList<KMAX>& L, const int k, float t, int obj, int face)
     return minT;
 }
 
-// walk_bvh_seq<false> with the list in place of the single survivor
+// walk_bvh_seq<false> (its select form, SEL) with the list in place of the single survivor
 template <int KMAX>
 DEV void walk_bvh_multi(const DevScene& S, int i, const int end, const Ray& r, HitList<KMAX>& L, const int k,
                         float& minT, const int obj) {
-    constexpr bool SEL = RTG_SEQ_SEL != 0;
     const RayRcp q = ray_rcp(r);
     while (i < end) {
         const float4 a = S.nodes[2 * i];
         const float4 b = S.nodes[2 * i + 1];
         const int skip = __float_as_int(b.z);
-        if (box_hit_fast<SEL>(a.x, a.y, a.z, a.w, b.x, b.y, r, q, minT)) {
+        if (box_hit_fast<true>(a.x, a.y, a.z, a.w, b.x, b.y, r, q, minT)) {
             const int leaf = __float_as_int(b.w);
             if (leaf >= 0) {
                 int first = leaf >> 8, cnt = leaf & 255;
@@ -88,8 +87,7 @@ DEV void walk_bvh_multi(const DevScene& S, int i, const int end, const Ray& r, H
                 }
                 for (int f = first; f < first + cnt; ++f) {
                     float t;
-                    if (SEL ? tri_test_sel(S.tris + 3 * f, r, minT, t) : tri_test_fast(S, f, r, minT, t))
-                        minT = list_insert(L, k, t, obj, f);
+                    if (tri_test_sel(S.tris + 3 * f, r, minT, t)) minT = list_insert(L, k, t, obj, f);
                 }
                 i = skip;
             } else {

@@ -9,7 +9,7 @@
 // (rtg_variants.hpp mega_variant) -- PT from the camera, MAXD from the scene's depth and the
 // Russian-roulette rule, the feature-specialised (SK, FEAT) sets under the same conditions.
 
-// the fused kernels keep trav_ray's ray unlaundered (rtg_common.hpp: laundering it costs C2
+// the fused kernels keep trav_ray's ray unlaundered (rtg_walk.hpp: laundering it costs C2
 // 6 %, profiles/r05ag_sphere_launder_ab.txt)
 #define RTG_XFORM_LAUNDER 0
 #include "rtg_common.hpp"

@@ -103,7 +103,7 @@ DEV int seg_append(bool want, int* lds_count) {
     return want ? base + __popcll(mask & ((1ull << lane) - 1ull)) : -1;
 }
 
-// SK: shading features the scene may use (rtg_common.hpp SK_*): the general variant and one
+// SK: shading features the scene may use (rtg_device.hpp SK_*): the general variant and one
 // without BRDFs and env / spot / mesh lights (C5: textures, point lights).
 #ifndef RTG_TREE_SHADE_WAVES_LEAN
 #define RTG_TREE_SHADE_WAVES_LEAN 2
@@ -476,7 +476,7 @@ __global__ __launch_bounds__(256) void k_tree_resolve(const DevScene S, const De
     }
     const float gw = sample_weight(C.spp, sample, root_key(P.seed, pixel, sample));
     float4 a = first ? make_float4(0.f, 0.f, 0.f, 0.f) : accum[pixel];
-    // (accum_samples, rtg_common.hpp: the same operations over a multi-sample pass's slabs)
+    // (accum_samples, rtg_frame.hpp: the same operations over a multi-sample pass's slabs)
     a.x += value.x * gw;
     a.y += value.y * gw;
     a.z += value.z * gw;

@@ -25,12 +25,6 @@ namespace rtg {
 
 enum { BASE_FINAL = 1, BASE_ADD_ZERO = 2 };
 
-// k_shade's environment-light directions searched by the whole wave (env_direction_wave);
-// 0: each lane's own loop (A/B)
-#ifndef RTG_ENV_WAVE
-#define RTG_ENV_WAVE 1
-#endif
-
 // ORD: RTG_RENDER_ORDERED (plain mesh scenes): the checked closest-hit walk on the any-hit tree
 // as wave packets (trace_closest_pk), the reference walk where its check fails
 #ifndef RTG_ORD_WAVES
@@ -58,7 +52,7 @@ __global__ __launch_bounds__(256, ORD ? RTG_ORD_WAVES : RTG_TRACE_WAVES(FEAT)) v
                 trace<false, STATS, FEAT>(S, ray, mbTime, INFINITY, INFINITY, h, cn);
             }
         } else if constexpr (DEFER) {
-            // large leaves deferred to k_bigleaf; k_hitfix settles the pixel (rtg_common.hpp DeferCtx)
+            // large leaves deferred to k_bigleaf; k_hitfix settles the pixel (rtg_walk.hpp DeferCtx)
             DeferCtx dc{W.dq_e, W.dq_count, W.dq_cap, i, false};
             trace<false, STATS, FEAT, true, true>(S, ray, mbTime, INFINITY, INFINITY, h, cn, &dc);
             if (dc.deferred) {
@@ -68,8 +62,7 @@ __global__ __launch_bounds__(256, ORD ? RTG_ORD_WAVES : RTG_TRACE_WAVES(FEAT)) v
                 return;
             }
         } else {
-            trace<false, STATS, FEAT, RTG_PRIMARY_PACKET != 0 && !(FEAT & FEAT_BIGLEAF)>(S, ray, mbTime, INFINITY,
-                                                                                       INFINITY, h, cn);
+            trace<false, STATS, FEAT, !(FEAT & FEAT_BIGLEAF)>(S, ray, mbTime, INFINITY, INFINITY, h, cn);
         }
         W.hit_t[i] = h.t;
         W.hit_obj[i] = h.obj;
@@ -109,7 +102,7 @@ __global__ __launch_bounds__(256) void k_bigleaf(const DevScene S, const WaveBuf
 
 // A pending pixel's hit from its key, checked: the winner's reference leaf box (and an
 // instance's world box) must pass the exact slab test at next_up(t) -- else the reference walk
-// decides (rtg_common.hpp DeferCtx).
+// decides (rtg_walk.hpp DeferCtx).
 // (diagnostics, RTG_DEFER_DIAG=1 only -- counters is null otherwise: extend_wide_visits counts
 // the pending pixels and extend_fallbacks those the check sent to the reference walk)
 template <int FEAT>
@@ -359,7 +352,7 @@ DEV f3 resolve_sum(f3 base, int flags, f3 sum) {
     return color;
 }
 
-// SK: shading variant (rtg_common.hpp SK_*).  MODE:
+// SK: shading variant (rtg_device.hpp SK_*).  MODE:
 //   SH_GENERAL  every light slot's term and occlusion flag to the per-pixel buffers, shadow
 //               rays to the block's queue segment (k_shadow, k_resolve follow);
 //   SH_ONE      at most one light with a shadow ray, and at most one environment light after
@@ -425,8 +418,7 @@ __global__ __launch_bounds__(256, MODE >= SH_FUSED ? (FAST ? RTG_WIDE_WAVES(FEAT
             ray = camera_ray<MOTION>(C, px, py, key, mbTime);
             cn.cam();
             Ray cr = ray;
-            trace<false, STATS, FEAT, RTG_PRIMARY_PACKET != 0 && !(FEAT & FEAT_BIGLEAF)>(S, cr, mbTime, INFINITY,
-                                                                                           INFINITY, fh, cn);
+            trace<false, STATS, FEAT, !(FEAT & FEAT_BIGLEAF)>(S, cr, mbTime, INFINITY, INFINITY, fh, cn);
         }
     }
     const int obj = FRAME ? fh.obj : (valid ? W.hit_obj[i] : -1);
@@ -623,11 +615,7 @@ __global__ __launch_bounds__(256, MODE >= SH_FUSED ? (FAST ? RTG_WIDE_WAVES(FEAT
     if constexpr ((SK & SK_XLIGHT) != 0) {
         for (int l = 0; l < S.num_env; ++l, ++slot) {
             // (the wave searches its lanes' directions together; every lane takes part)
-#if RTG_ENV_WAVE
             const f3 sd = env_direction_wave(S, lit ? n : mk(0, 0, 1), key, l, lit);
-#else
-            const f3 sd = lit ? env_direction(S, n, key, l) : mk(0, 0, 0);
-#endif
             if (lit) {                                               // no shadow ray (:741-755)
                 put(shade<false, SK>(S, c, n, w_o, env_sample(S, l, sd)));
                 if (!ONE) W.occ[slot] = 0;

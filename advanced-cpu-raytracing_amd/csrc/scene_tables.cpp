@@ -270,7 +270,7 @@ int object_table(const rtg_scene_desc* d, SceneTables& T) {
     return feat;
 }
 
-// Shadow-ray acceleration (rtg_common.hpp): the any-hit wide BVH (trace_any_wide) and
+// Shadow-ray acceleration (rtg_anyhit.hpp): the any-hit wide BVH (trace_any_wide) and
 // face -> reference leaf (its exact leaf-box decisions, the deferred leaves' checks), from the
 // walk records nd / nx and the face records tris.
 void shadow_tables(const rtg_scene_desc* d, const TableOptions& opt, const std::vector<float4>& nd,
@@ -586,7 +586,7 @@ bool any_mapped(const rtg_scene_desc* d) {
 namespace {
 // validate_desc; `geometry` false: without the checks that read faces, nodes or texels
 int validate(const rtg_scene_desc* d, bool geometry, std::string& err) {
-    // the packet walks address records by 32-bit byte offsets (rtg_common.hpp rec_at)
+    // the packet walks address records by 32-bit byte offsets (rtg_isect.hpp rec_at)
     if (geometry && d->num_faces > ((int64_t)1 << 25))
         return fail(err, RTG_ERR_INVALID, "%lld faces: at most 2^25 per scene", (long long)d->num_faces);
     for (int i = 0; i < d->num_mesh_lights; ++i) {

@@ -343,7 +343,7 @@ def config_defer_gate(out_dir: str, pad_objects: int = 0, pad_faces: int = 0, K:
     BEFORE it in object order, behind the camera: ``pad_objects`` one-face meshes and one mesh of
     ``pad_faces`` faces (a height field).  They push the blob's object index and its faces'
     record indices up to the limits of the deferred-leaf key (12 object bits, 20 face bits;
-    rtg_common.hpp obj_key, gate in rtg_wave.hpp) without changing the image."""
+    rtg_isect.hpp obj_key, gate in rtg_wave.hpp) without changing the image."""
     os.makedirs(out_dir, exist_ok=True)
     v, f = blob_mesh(K, center=(0, 1.0, 0), radius=1.0, seed=7)
     write_ply(os.path.join(out_dir, "gate_blob.ply"), v, f)

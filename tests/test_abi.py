@@ -142,7 +142,7 @@ def _desc_layout(tmp_path):
 def test_face_limit_refused(tmp_path):
     """rtg_scene_create refuses descriptions of more than 2^25 faces with RTG_ERR_INVALID
     before touching a device (rtg_api.cpp: the packet walks address node and face records by
-    32-bit byte offsets, rtg_common.hpp rec_at).  The description is a real one with its face
+    32-bit byte offsets, rtg_isect.hpp rec_at).  The description is a real one with its face
     list replaced by 2^25 + 1 zeroed faces (calloc'd: untouched pages cost nothing)."""
     size, off_faces, off_num, face_size = _desc_layout(tmp_path)
     assert face_size == 80

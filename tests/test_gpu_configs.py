@@ -158,7 +158,7 @@ def test_large_leaf_cooperative_walk_small(cfg, in_tmp):
 @pytest.mark.parametrize("name", ["c3_small", "c4_small", "c3_blob", "berserker", "windmill", "tower", "car_smooth"])
 def test_deferred_large_leaves(name, in_tmp, monkeypatch):
     """Large-leaf scenes: the camera walk defers its large leaves to k_bigleaf and settles each
-    pixel in k_hitfix (the winner's leaf box checked at next_up(t), rtg_common.hpp DeferCtx), the
+    pixel in k_hitfix (the winner's leaf box checked at next_up(t), rtg_walk.hpp DeferCtx), the
     shadow walk queues its large leaves to k_bigleaf_any (AnyDefer) -- bit for bit the image of the cooperative
     reference walk (RTG_DEFER=0), of camera deferral alone (RTG_DEFER_ANY=0) and of the counting
     render (which never defers)."""
@@ -192,7 +192,7 @@ def test_deferred_large_leaves(name, in_tmp, monkeypatch):
     ("faces_over", 0, 2 ** 20, False),         # the blob's face records start past 2^20
 ])
 def test_deferral_gate(case, pad_objects, pad_faces, deferred, in_tmp, monkeypatch):
-    """The deferred-leaf key packs (t, object, face) into 32 + 12 + 20 bits (rtg_common.hpp
+    """The deferred-leaf key packs (t, object, face) into 32 + 12 + 20 bits (rtg_isect.hpp
     obj_key), so the camera walk defers only scenes of fewer than 4 096 objects and 2^20 faces
     (rtg_wave.hpp launch_wave_t).  Padding meshes before the large-leaf blob put its object index
     and face records on either side of those limits: below them the deferring walk runs (pending

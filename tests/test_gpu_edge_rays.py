@@ -184,9 +184,8 @@ def test_nonfinite_rays(name, tmp_path_factory):
         lane's node index grows every step as above and the lane retires at `end`.
         coop_leaf_tests loops over at most 64 events, over the sum of their leaf counts, and a
         binary search over the events.
-      walk_bvh_packet: one wave-uniform node index that goes to i + 1, to the record's skip, or
-        (any-hit lanes all finished) to the minimum of the lanes' resume indices, each above i,
-        until `end`; leaves as above.
+      walk_bvh_packet: one wave-uniform node index that goes to i + 1 or to the record's skip,
+        each above i, until `end`; leaves as above.
       walk_wide_any_pk: an explicit step counter (RTG_PK_MAX_STEPS) and a stack of
         RTG_PK_STACK entries that only pops between descents; a ray whose direction is off the
         fast range, or whose o * rcp(d) is not finite, never walks (it is undecided at once and

@@ -1,4 +1,4 @@
-"""The packet walks' fused slab distances (csrc/rtg_common.hpp SlabFma: t = fma(m, inv, -fl(o inv)))
+"""The packet walks' fused slab distances (csrc/rtg_isect.hpp SlabFma: t = fma(m, inv, -fl(o inv)))
 on the scenes where their new absolute error term, 2^-24 max|o inv|, matters most: a far origin,
 near-axis camera rays, a grazing far light and an instanced mesh.  Small height fields (1 000
 triangles) built here with scenes.heightfield_mesh / scenes.write_ply and an XML of the shape of

@@ -1,4 +1,4 @@
-"""The leaf-exact camera packet walk (rtg_common.hpp walk_bvh_packet_lx: conservative decisions at
+"""The leaf-exact camera packet walk (rtg_walk.hpp walk_bvh_packet_lx: conservative decisions at
 inner nodes, the exact one at leaves) against walks it does not touch: the per-lane fused kernel
 (RTG_RENDER_FUSED, k_render), the host walk (HostScene.trace) and the oracle; counting renders keep
 the walk that is exact at every node and must report the oracle's counters.  Every render case

@@ -1,4 +1,4 @@
-"""Ordered closest hit (RTG_RENDER_ORDERED: rtg_common.hpp trace_closest_pk on the any-hit tree
+"""Ordered closest hit (RTG_RENDER_ORDERED: rtg_anyhit.hpp trace_closest_pk on the any-hit tree
 as wave packets) against the
 reference-order walk it replaces for camera rays of plain mesh scenes.
 

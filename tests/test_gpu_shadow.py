@@ -1,5 +1,5 @@
 """k_shadow's walk against the per-lane reference-order walk (RTG_RENDER_EXACT_SHADOW).
-The shipped wavefront walk (RTG_SHADOW_MODE 3, rtg_common.hpp trace_any_wide) decides
+The shipped wavefront walk (RTG_SHADOW_MODE 3, rtg_anyhit.hpp trace_any_wide) decides
 CastShadowRay (raytracer.cpp:585-623, a boolean) on the any-hit tree (rtg_ahb.cpp: binned
 SAH over the reference's leaves), by exact sufficient / necessary conditions on each face's
 reference leaf box with a reference-walk fallback; the A/B trees (RTG_AHB=split: large leaves

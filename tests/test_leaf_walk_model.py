@@ -1,4 +1,4 @@
-"""A numpy MODEL of the leaf-exact closest-hit packet walk (csrc/rtg_common.hpp: walk_bvh_packet_lx;
+"""A numpy MODEL of the leaf-exact closest-hit packet walk (csrc/rtg_walk.hpp: walk_bvh_packet_lx;
 DESIGN.md §2 "Leaf-exact walks").  It models the device code and does not run it.
 
 The lemma: in the reference's pre-order walk a ray tests the faces of leaf L iff L's own box passes
@@ -37,7 +37,7 @@ ALL_SCENES = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(SCE
 MODEL_SCENES = ["edge_lattice", "edge_roof", "transforms_textures"]
 N_CAMERA = 1536
 
-# --- constants of csrc/rtg_common.hpp
+# --- constants of csrc/rtg_isect.hpp and csrc/rtg_walk.hpp
 TINY = F(1e-30)
 CONS_BIAS = F(2.0 ** -22)        # slab_cons_ray: e_k = 2^-22 |o_k inv_k|
 CONS_REL = F(2.0 ** -20)         # slab_cons_pk: 1 - 2^-20; minTc = minT (1 + 2^-20)

@@ -1,4 +1,4 @@
-"""A numpy MODEL of the packet walks' fused slab predicates (csrc/rtg_common.hpp: SlabFma,
+"""A numpy MODEL of the packet walks' fused slab predicates (csrc/rtg_isect.hpp: SlabFma,
 box_pass_t / box_pass_v, slab_cons_v).  It models the device code and does not run it: the
 constants below are copied from the header, the arithmetic is restated in float32 with the FMA
 emulated through float64 (the product of two floats is exact there), and the reciprocal is the
@@ -15,7 +15,7 @@ import pytest
 F = np.float32
 N = 1_000_000
 
-# --- constants of csrc/rtg_common.hpp
+# --- constants of csrc/rtg_isect.hpp
 REL_SLACK = F(2.0 ** -20)        # box_pass_t: relative slack of the exact decisions
 ABS_SLACK = F(2.0 ** -21)        # slab_slack0: slack0 = 1e-30 + 2^-21 A
 TINY = F(1e-30)
@@ -84,7 +84,7 @@ def box_pass(lo, hi, o, d, inv, minT):
     return sure, ans
 
 
-def slab_cons(lo, hi, o, inv, minT0):
+def slab_cons_v(lo, hi, o, inv, minT0):
     """slab_cons_v on slab_cons_ray's per-axis constants: the axis's entry distance lowered and its
     exit distance raised by e_k (a_k goes with the box minimum, b_k with the maximum)."""
     with np.errstate(all="ignore"):
@@ -152,7 +152,7 @@ def test_fused_slab_predicates(scale):
         lo, hi, o, d, inv, minT = pairs(scale, limit_kind, seed=int(scale) * 10 + len(limit_kind))
         exact = box_hit(lo, hi, o, d, minT)
         sure, ans = box_pass(lo, hi, o, d, inv, minT)
-        cons = slab_cons(lo, hi, o, inv, minT)
+        cons = slab_cons_v(lo, hi, o, inv, minT)
         n_wrong = int(np.sum(sure & (ans != exact)))
         n_lost = int(np.sum(exact & ~cons))
         print(f"scale {scale:g} limit {limit_kind}: sure {np.mean(sure):.3f}, exact keeps {np.mean(exact):.3f}, "

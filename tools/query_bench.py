@@ -88,7 +88,7 @@ def radiance_section(args, name, xml):
     torch.cuda.synchronize()
     g = torch.Generator(device="cpu").manual_seed(1234)
     perm = torch.randperm(n, generator=g)
-    # k_primary's wave shape (rtg_common.hpp tile_pixel): 64 consecutive rays = one 8x8 pixel tile
+    # k_primary's wave shape (rtg_frame.hpp tile_pixel): 64 consecutive rays = one 8x8 pixel tile
     assert w % 8 == 0 and h % 8 == 0
     yy, xx = np.divmod(np.arange(n), w)
     key = (yy // 8) * (w // 8) * 64 + (xx // 8) * 64 + (yy % 8) * 8 + (xx % 8)
@@ -189,7 +189,7 @@ def surface_section(args, name, xml, min_rays):
     pixel = rays0.repeat(rep, 1).contiguous()
     sets = {"pixel": pixel}
     if w % 8 == 0 and h % 8 == 0:
-        # k_primary's wave shape (rtg_common.hpp tile_pixel): 64 consecutive rays = one 8x8 pixel tile
+        # k_primary's wave shape (rtg_frame.hpp tile_pixel): 64 consecutive rays = one 8x8 pixel tile
         yy, xx = np.divmod(np.arange(n0), w)
         key = (yy // 8) * (w // 8) * 64 + (xx // 8) * 64 + (yy % 8) * 8 + (xx % 8)
         order = np.empty(n0, np.int64)
@@ -591,7 +591,7 @@ def query_main(args):
     torch.cuda.synchronize()
     g = torch.Generator(device="cpu").manual_seed(1234)
     permuted = rays[torch.randperm(n, generator=g).to(dev)].contiguous()
-    # k_primary's wave shape (rtg_common.hpp tile_pixel): 64 consecutive rays = one 8x8 pixel tile
+    # k_primary's wave shape (rtg_frame.hpp tile_pixel): 64 consecutive rays = one 8x8 pixel tile
     assert w % 16 == 0 and h % 8 == 0
     yy, xx = np.divmod(np.arange(n), w)
     key = (yy // 8) * (w // 8) * 64 + (xx // 8) * 64 + (yy % 8) * 8 + (xx % 8)
