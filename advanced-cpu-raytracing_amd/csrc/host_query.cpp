@@ -16,6 +16,10 @@
 //
 // rtg_desc_closest_points: the nearest surface point to a point (closest_one below).  No reference
 // code stands behind it: this walk is the definition that k_closest (rtg_closest.hip) repeats.
+//
+// rtg_desc_count_crossings: the multi-hit walk counting every accepted hit instead of keeping k
+// (cross_one below); rtg_desc_signed_distance_points: closest_one, then cross_one from the point
+// (signed_one).  Both define what k_crossings / k_signed_distance (rtg_crossings.hip) repeat.
 #include "host_query.hpp"
 
 #include <algorithm>
@@ -332,6 +336,95 @@ void multi_one(const rtg_scene_desc* d, const rtg_ray& q, int kk, rtg_hit* out, 
     if (count) *count = L.n;
 }
 
+// ---- crossing counts (rtg_desc_count_crossings): multi_one's walk with nothing kept, so minT is
+// tmax from start to end and every accepted hit is counted.  No reference code: this walk is the
+// definition that k_crossings (rtg_crossings.hip) repeats.
+
+struct CrossWalk {
+    const rtg_bvh_node* nodes;
+    const rtg_face* faces;
+    HRay r;                       // local ray
+    float tmax;
+    rtg_crossings* C;
+};
+
+// BVH::IntersectBVH, every accepted face counted; it enters where the local ray goes against
+// the face's normal
+void intersect_bvh_cross(CrossWalk& w, int k) {
+    const rtg_bvh_node& n = w.nodes[k];
+    if (!box_hit(n.bmin, n.bmax, w.r, w.tmax)) return;
+    if (n.left < 0) {
+        for (int i = n.first; i < n.first + n.count; ++i) {
+            float t;
+            if (face_hit(w.faces[i], w.r, w.tmax, t)) {
+                w.C->count += 1;
+                if (dot(w.r.d, from_f3(w.faces[i].n)) < 0.0f) w.C->entering += 1;
+            }
+        }
+    } else {
+        intersect_bvh_cross(w, n.left);
+        intersect_bvh_cross(w, n.left + 1);
+    }
+}
+
+// Sphere::Intersect's two roots, sphere_hit's arithmetic: `in` = (-b - delta) / a, where the ray
+// enters, `out` the other.  False: no real root.
+bool sphere_in_out(const rtg_object& ob, const HRay& lr, float& in, float& out) {
+    const V3 center = from_f3(ob.center);
+    V3 oc = lr.o - center;
+    float c = dot(oc, oc) - (ob.radius * ob.radius);
+    float b = 2 * dot(lr.d, oc);
+    float a = dot(lr.d, lr.d);
+    float delta = b * b - (4 * a * c);
+    if (delta < 0.0f) return false;
+    delta = sqrtf(delta);
+    a = (float)(2.0 * a);
+    out = (-b + delta) / a;
+    in = (-b - delta) / a;
+    return true;
+}
+
+// multi_one's object loop on two counters
+void cross_one(const rtg_scene_desc* d, const rtg_ray& q, rtg_crossings& C) {
+    HRay r;
+    r.o = V3(q.ox, q.oy, q.oz);
+    r.d = V3(q.dx, q.dy, q.dz);
+    const float time = q.time, tmax = q.tmax;
+    C.count = 0;
+    C.entering = 0;
+    for (int k = 0; k < d->num_objects; ++k) {
+        const rtg_object& ob = d->objects[k];
+        if (ob.kind == RTG_OBJ_SPHERE) {
+            // multi_one takes the selected root, then the other if it differs, each under
+            // t > 0 && t < minT: with minT fixed that is each distinct root under the same test
+            float in, out;
+            if (sphere_in_out(ob, local_ray(ob, r, time), in, out)) {
+                if (in < tmax && in > 0.0f) { C.count += 1; C.entering += 1; }
+                if (out != in && out < tmax && out > 0.0f) C.count += 1;
+            }
+            continue;
+        }
+        const rtg_mesh& M = d->meshes[ob.mesh];
+        if (ob.kind == RTG_OBJ_INSTANCE) {
+            HRay wr = r;
+            if (ob.flags & RTG_OBJF_MOTION_BLUR) wr.o = wr.o + from_f3(ob.motion_blur) * time;
+            if (!box_hit(ob.bbox_min, ob.bbox_max, wr, tmax)) {
+                r.o = wr.o;
+                continue;
+            }
+        }
+        CrossWalk w;
+        w.nodes = d->nodes + M.node_offset;
+        w.faces = d->faces + M.face_offset;
+        w.r = local_ray(ob, r, time);
+        w.tmax = tmax;
+        w.C = &C;
+        if (ob.kind == RTG_OBJ_MESH && !box_hit(ob.bbox_min, ob.bbox_max, w.r, tmax)) continue;
+        if (M.node_count <= 0) continue;
+        intersect_bvh_cross(w, 0);
+    }
+}
+
 // ---- closest-point queries (rtg_desc_closest_points): the nearest surface point to a point.
 // No ray and no reference code: rtgpu.h states the semantics, this walk defines them operation by
 // operation, and k_closest (rtg_closest.hip) repeats its decisions with the same arithmetic.
@@ -497,6 +590,20 @@ void closest_one(const rtg_scene_desc* d, const PointXf* xf, const rtg_point& q,
     out.pad1 = 0.f;
 }
 
+// rtg_desc_signed_distance_points: closest_one, then cross_one from the point along dir (unbounded,
+// time 0); the count into pad0, an odd one onto a hit's sign bit.  A point that is not finite
+// walks nothing.
+void signed_one(const rtg_scene_desc* d, const PointXf* xf, const rtg_point& q, const float* dir, rtg_nearest& out) {
+    closest_one(d, xf, q, out);
+    const bool finite = fabsf(q.x) < INFINITY && fabsf(q.y) < INFINITY && fabsf(q.z) < INFINITY;
+    if (!finite) return;
+    const rtg_ray ray = {q.x, q.y, q.z, INFINITY, dir[0], dir[1], dir[2], 0.0f};
+    rtg_crossings C;
+    cross_one(d, ray, C);
+    out.pad0 = C.count;
+    if (out.object >= 0 && (C.count & 1)) out.dist = -out.dist;
+}
+
 // fn(begin, end) over [0, n) in contiguous chunks on a few threads: rays are independent
 template <typename Fn>
 void chunked(int64_t n, Fn&& work) {
@@ -566,6 +673,50 @@ int host_closest_points(const rtg_scene_desc* d, const rtg_point* points, int64_
     if (int rc = closest_unsupported(xf.data(), d->num_objects, err)) return rc;
     chunked(n, [&](int64_t b, int64_t e) {
         for (int64_t i = b; i < e; ++i) closest_one(d, xf.data(), points[i], out[i]);
+    });
+    return RTG_OK;
+}
+
+int host_count_crossings(const rtg_scene_desc* d, const rtg_ray* rays, int64_t n, uint32_t flags, rtg_crossings* out,
+                         std::string& err) {
+    if (!d) { err = "null description"; return RTG_ERR_INVALID; }
+    if (n < 0 || n > INT32_MAX) { err = "ray count out of range"; return RTG_ERR_INVALID; }
+    if (flags & RTG_QUERY_ANY_HIT) { err = "RTG_QUERY_ANY_HIT does not apply to a crossing count"; return RTG_ERR_INVALID; }
+    if (flags & ~(uint32_t)RTG_QUERY_COHERENT) { err = "unknown query flags"; return RTG_ERR_INVALID; }
+    if (const char* e = check_desc(d)) { err = e; return RTG_ERR_INVALID; }
+    if (n == 0) return RTG_OK;
+    if (!rays || !out) { err = "null buffer"; return RTG_ERR_INVALID; }
+    chunked(n, [&](int64_t b, int64_t e) {
+        for (int64_t i = b; i < e; ++i) cross_one(d, rays[i], out[i]);
+    });
+    return RTG_OK;
+}
+
+const char* signed_distance_dir(const float* dir, float out[3]) {
+    static const float kDefault[3] = {0.8213f, 0.4402f, 0.3628f};
+    const float* v = dir ? dir : kDefault;
+    for (int j = 0; j < 3; ++j) {
+        if (!(fabsf(v[j]) < INFINITY)) return "dir is not finite";
+        out[j] = v[j];
+    }
+    if (v[0] == 0.f && v[1] == 0.f && v[2] == 0.f) return "dir is all zero";
+    return nullptr;
+}
+
+int host_signed_distance_points(const rtg_scene_desc* d, const rtg_point* points, int64_t n, const float* dir,
+                                uint32_t flags, rtg_nearest* out, std::string& err) {
+    if (!d) { err = "null description"; return RTG_ERR_INVALID; }
+    if (n < 0 || n > INT32_MAX) { err = "point count out of range"; return RTG_ERR_INVALID; }
+    if (flags) { err = "unknown query flags"; return RTG_ERR_INVALID; }
+    if (const char* e = check_desc(d)) { err = e; return RTG_ERR_INVALID; }
+    if (n > 0 && (!points || !out)) { err = "null buffer"; return RTG_ERR_INVALID; }
+    float v[3];
+    if (const char* e = signed_distance_dir(dir, v)) { err = e; return RTG_ERR_INVALID; }
+    std::vector<PointXf> xf((size_t)d->num_objects);
+    for (int i = 0; i < d->num_objects; ++i) point_xf_record(d->objects[i], xf[i]);
+    if (int rc = closest_unsupported(xf.data(), d->num_objects, err)) return rc;
+    chunked(n, [&](int64_t b, int64_t e) {
+        for (int64_t i = b; i < e; ++i) signed_one(d, xf.data(), points[i], v, out[i]);
     });
     return RTG_OK;
 }

@@ -28,4 +28,15 @@ int host_closest_points(const rtg_scene_desc* d, const rtg_point* points, int64_
 struct PointXf;
 int closest_unsupported(const PointXf* xf, int num_objects, std::string& err);
 
+// Crossing counts (rtgpu.h rtg_desc_count_crossings): per ray the number of accepted hits and how
+// many of them enter, by the walk that defines the query (the yardstick of k_crossings).
+int host_count_crossings(const rtg_scene_desc* d, const rtg_ray* rays, int64_t n, uint32_t flags, rtg_crossings* out,
+                         std::string& err);
+// Signed distances (rtgpu.h rtg_desc_signed_distance_points): the closest-point walk, then the
+// crossing walk from the point along dir (nullable: the default direction).
+int host_signed_distance_points(const rtg_scene_desc* d, const rtg_point* points, int64_t n, const float* dir,
+                                uint32_t flags, rtg_nearest* out, std::string& err);
+// dir (nullable: the documented default) into out[3]; null, or what is wrong with it
+const char* signed_distance_dir(const float* dir, float out[3]);
+
 }  // namespace rtg

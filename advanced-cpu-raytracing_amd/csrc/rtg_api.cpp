@@ -1268,6 +1268,75 @@ int rtg_closest_points(rtg_scene* s, const rtg_point* points, int64_t n, uint32_
     return unstage(s, bufs);
 }
 
+// ---- crossing counts and signed distances (rtg_crossings.hip)
+static int crossings_args(const rtg_scene* s, const void* rays, int64_t n, uint32_t flags, const void* out) {
+    if (!s) return set_err(RTG_ERR_INVALID, "null scene");
+    if (n < 0 || n > INT32_MAX) return set_err(RTG_ERR_INVALID, "%lld rays: at most INT32_MAX per call", (long long)n);
+    if (flags & RTG_QUERY_ANY_HIT) return set_err(RTG_ERR_INVALID, "RTG_QUERY_ANY_HIT does not apply to a crossing count");
+    if (flags & ~(uint32_t)RTG_QUERY_COHERENT) return set_err(RTG_ERR_INVALID, "unknown query flags 0x%x", flags);
+    if (n > 0 && (!rays || !out)) return set_err(RTG_ERR_INVALID, "null buffer");
+    return RTG_OK;
+}
+
+int rtg_count_crossings_device(rtg_scene* s, const rtg_ray* d_rays, int64_t n, uint32_t flags, rtg_crossings* d_out,
+                               void* stream) {
+    int rc = crossings_args(s, d_rays, n, flags, d_out);
+    if (rc || n == 0) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(rtg::launch_crossings(s->ds, s->feat, d_rays, (int)n, d_out, (hipStream_t)stream));
+    return RTG_OK;
+}
+
+int rtg_count_crossings(rtg_scene* s, const rtg_ray* rays, int64_t n, uint32_t flags, rtg_crossings* out) {
+    int rc = crossings_args(s, rays, n, flags, out);
+    if (rc || n == 0) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t N = (size_t)n;
+    const std::initializer_list<Staged> bufs = {{Q_RAYS, N * sizeof(rtg_ray), rays, nullptr},
+                                                {Q_COUNTS, N * sizeof(rtg_crossings), nullptr, out}};
+    if ((rc = stage(s, bufs))) return rc;
+    HIP_TRY(rtg::launch_crossings(s->ds, s->feat, (rtg_ray*)s->q[Q_RAYS].p, (int)n, (rtg_crossings*)s->q[Q_COUNTS].p,
+                                  s->stream));
+    return unstage(s, bufs);
+}
+
+// closest_args with the direction between the argument errors and the ellipsoid refusal
+static int signed_distance_args(const rtg_scene* s, const void* points, int64_t n, const float* dir, uint32_t flags,
+                                const void* out, float v[3]) {
+    if (!s) return set_err(RTG_ERR_INVALID, "null scene");
+    if (n < 0 || n > INT32_MAX) return set_err(RTG_ERR_INVALID, "%lld points: at most INT32_MAX per call", (long long)n);
+    if (flags) return set_err(RTG_ERR_INVALID, "unknown query flags 0x%x", flags);
+    if (n > 0 && (!points || !out)) return set_err(RTG_ERR_INVALID, "null buffer");
+    if (const char* e = rtg::signed_distance_dir(dir, v)) return set_err(RTG_ERR_INVALID, "%s", e);
+    return closest_args(s, points, n, flags, out);
+}
+
+int rtg_signed_distance_points_device(rtg_scene* s, const rtg_point* d_points, int64_t n, const float dir[3],
+                                      uint32_t flags, rtg_nearest* d_out, void* stream) {
+    float v[3];
+    int rc = signed_distance_args(s, d_points, n, dir, flags, d_out, v);
+    if (rc || n == 0) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(rtg::launch_signed_distance(s->ds, s->point_xf.ptr(), s->closest_feat, d_points, (int)n, v, d_out,
+                                        (hipStream_t)stream));
+    return RTG_OK;
+}
+
+int rtg_signed_distance_points(rtg_scene* s, const rtg_point* points, int64_t n, const float dir[3], uint32_t flags,
+                               rtg_nearest* out) {
+    float v[3];
+    int rc = signed_distance_args(s, points, n, dir, flags, out, v);
+    if (rc || n == 0) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t N = (size_t)n;
+    const std::initializer_list<Staged> bufs = {{Q_POINTS, N * sizeof(rtg_point), points, nullptr},
+                                                {Q_NEAREST, N * sizeof(rtg_nearest), nullptr, out}};
+    if ((rc = stage(s, bufs))) return rc;
+    HIP_TRY(rtg::launch_signed_distance(s->ds, s->point_xf.ptr(), s->closest_feat, (rtg_point*)s->q[Q_POINTS].p, (int)n,
+                                        v, (rtg_nearest*)s->q[Q_NEAREST].p, s->stream));
+    return unstage(s, bufs);
+}
+
 // the camera record and row range of a camera-ray batch
 static int camera_rays_args(const rtg_scene* s, const rtg_render_opts* o, const void* rays, rtg::DevCamera& C,
                             int& row_begin, int& row_end) {
@@ -1429,6 +1498,30 @@ int rtg_desc_closest_points(const rtg_scene_desc* d, const rtg_point* points, in
         rc = rtg::host_closest_points(d, points, n, flags, out, err);
     } catch (const std::exception& e) {
         return set_err(RTG_ERR_NOMEM, "rtg_desc_closest_points: %s", e.what());
+    }
+    return rc == RTG_OK ? RTG_OK : set_err(rc, "%s", err.c_str());
+}
+
+int rtg_desc_count_crossings(const rtg_scene_desc* d, const rtg_ray* rays, int64_t n, uint32_t flags,
+                             rtg_crossings* out) {
+    std::string err;
+    int rc;
+    try {
+        rc = rtg::host_count_crossings(d, rays, n, flags, out, err);
+    } catch (const std::exception& e) {
+        return set_err(RTG_ERR_NOMEM, "rtg_desc_count_crossings: %s", e.what());
+    }
+    return rc == RTG_OK ? RTG_OK : set_err(rc, "%s", err.c_str());
+}
+
+int rtg_desc_signed_distance_points(const rtg_scene_desc* d, const rtg_point* points, int64_t n, const float dir[3],
+                                    uint32_t flags, rtg_nearest* out) {
+    std::string err;
+    int rc;
+    try {
+        rc = rtg::host_signed_distance_points(d, points, n, dir, flags, out, err);
+    } catch (const std::exception& e) {
+        return set_err(RTG_ERR_NOMEM, "rtg_desc_signed_distance_points: %s", e.what());
     }
     return rc == RTG_OK ? RTG_OK : set_err(rc, "%s", err.c_str());
 }

@@ -78,6 +78,15 @@ hipError_t launch_multihit(const DevScene& S, int feat, const rtg_ray* rays, int
 // per lane; xf: the per-object placement records (rtg_pointxf.hpp), num_objects of them.
 hipError_t launch_closest(const DevScene& S, const PointXf* xf, int feat, const rtg_point* points, int n,
                           rtg_nearest* out, hipStream_t stream);
+// crossing counts (rtg_crossings.hip): per ray the number of hits with 0 < t < tmax and how many of
+// them enter, one ray per lane; no bound on the number.
+hipError_t launch_crossings(const DevScene& S, int feat, const rtg_ray* rays, int n, rtg_crossings* out,
+                            hipStream_t stream);
+// signed distances (rtg_crossings.hip): launch_closest's record per point, then the crossing walk
+// from the point along dir (three floats, host memory, passed by value): the count in pad0, an odd
+// one on a hit's sign bit.  feat: launch_closest's (a superset of the ray walks').
+hipError_t launch_signed_distance(const DevScene& S, const PointXf* xf, int feat, const rtg_point* points, int n,
+                                  const float dir[3], rtg_nearest* out, hipStream_t stream);
 // surface queries (rtg_surface.hip): closest hit of n rays, one ray per lane, with the hit's shading
 // normal (normal / bump maps applied), texture coordinates, geometric normal, material and
 // GetDiffuse's coefficient; flags: RTG_QUERY_COHERENT only.  sk / feat as for launch_mega (a scene

@@ -49,6 +49,10 @@ SURFACE_DTYPE = np.dtype([("t", "<f4"), ("object", "<i4"), ("face", "<i4"), ("ma
 POINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("max_dist", "<f4")])
 NEAREST_DTYPE = np.dtype([("dist", "<f4"), ("object", "<i4"), ("face", "<i4"), ("pad0", "<i4"),
                           ("p", "<f4", (3,)), ("pad1", "<f4")])
+# rtg_crossings (8 B) of the crossing-count queries
+CROSSINGS_DTYPE = np.dtype([("count", "<i4"), ("entering", "<i4")])
+# the direction rtg_signed_distance_points* walks along when given none (rtgpu.h)
+SDF_DEFAULT_DIRECTION = (0.8213, 0.4402, 0.3628)
 RTG_CAMERA_SIZE = 392   # sizeof(rtg_camera), checked against the C compiler by tests/test_abi.py
 
 
@@ -183,6 +187,8 @@ EXPORTED = [
     "rtg_trace_rays_device", "rtg_trace_rays", "rtg_camera_rays_device", "rtg_camera_rays", "rtg_desc_trace_rays",
     "rtg_trace_rays_multi_device", "rtg_trace_rays_multi", "rtg_desc_trace_rays_multi",
     "rtg_closest_points_device", "rtg_closest_points", "rtg_desc_closest_points",
+    "rtg_count_crossings_device", "rtg_count_crossings", "rtg_desc_count_crossings",
+    "rtg_signed_distance_points_device", "rtg_signed_distance_points", "rtg_desc_signed_distance_points",
     "rtg_radiance_rays_device", "rtg_radiance_rays",
     "rtg_surface_rays_device", "rtg_surface_rays",
     "rtg_scene_update", "rtg_scene_set_camera", "rtg_scene_num_cameras", "rtg_camera_setup",
@@ -256,6 +262,12 @@ def lib() -> ctypes.CDLL:
     L.rtg_closest_points_device.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_uint32, vp, vp]
     L.rtg_closest_points.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_uint32, vp]
     L.rtg_desc_closest_points.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_uint32, vp]
+    L.rtg_count_crossings_device.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_uint32, vp, vp]
+    L.rtg_count_crossings.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_uint32, vp]
+    L.rtg_desc_count_crossings.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_uint32, vp]
+    L.rtg_signed_distance_points_device.argtypes = [vp, vp, ctypes.c_int64, vp, ctypes.c_uint32, vp, vp]
+    L.rtg_signed_distance_points.argtypes = [vp, vp, ctypes.c_int64, vp, ctypes.c_uint32, vp]
+    L.rtg_desc_signed_distance_points.argtypes = [vp, vp, ctypes.c_int64, vp, ctypes.c_uint32, vp]
     L.rtg_radiance_rays_device.argtypes =[vp, P(RadianceOpts), vp, vp, ctypes.c_int64, vp, vp]
     L.rtg_radiance_rays.argtypes = [vp, P(RadianceOpts), vp, vp, ctypes.c_int64, vp]
     L.rtg_surface_rays_device.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_uint32, vp, vp]
@@ -331,6 +343,28 @@ def _query_closest(fn, handle, points):
     return out
 
 
+def _query_crossings(fn, handle, rays, coherent):
+    """Shared body of HostScene.crossings / DeviceScene.crossings."""
+    rays = np.ascontiguousarray(rays, RAY_DTYPE)
+    out = np.zeros(rays.size, CROSSINGS_DTYPE)
+    _check(fn(handle, rays.ctypes.data, rays.size, _query_flags(False, coherent), out.ctypes.data))
+    return out
+
+
+def _direction(direction):
+    """None (the library's default), or three float32 the call keeps alive."""
+    return None if direction is None else np.ascontiguousarray(direction, np.float32).reshape(3)
+
+
+def _query_signed_distance(fn, handle, points, direction):
+    """Shared body of HostScene.signed_distance / DeviceScene.signed_distance."""
+    points = np.ascontiguousarray(points, POINT_DTYPE)
+    out = np.zeros(points.size, NEAREST_DTYPE)
+    d = _direction(direction)
+    _check(fn(handle, points.ctypes.data, points.size, None if d is None else d.ctypes.data, 0, out.ctypes.data))
+    return out
+
+
 def device_count() -> int:
     n = ctypes.c_int32()
     _check(lib().rtg_device_count(ctypes.byref(n)))
@@ -403,6 +437,19 @@ class HostScene:
         (rtg_desc_closest_points: the walk that defines the query, the yardstick of
         DeviceScene.closest).  Returns the NEAREST_DTYPE array."""
         return _query_closest(lib().rtg_desc_closest_points, self.desc, points)
+
+    def crossings(self, rays):
+        """How many surfaces each ray meets with 0 < t < tmax, and at how many of them it enters, on
+        the host, no device (rtg_desc_count_crossings: the walk that defines the query, the
+        yardstick of DeviceScene.crossings).  Returns the CROSSINGS_DTYPE array."""
+        return _query_crossings(lib().rtg_desc_count_crossings, self.desc, rays, False)
+
+    def signed_distance(self, points, direction=None):
+        """closest() with the distance signed by the parity of the surfaces crossed from the point
+        along ``direction`` (three floats; None: the library's default), on the host, no device
+        (rtg_desc_signed_distance_points: the yardstick of DeviceScene.signed_distance).  ``pad0``
+        carries the crossing count."""
+        return _query_signed_distance(lib().rtg_desc_signed_distance_points, self.desc, points, direction)
 
     def num_cameras(self) -> int:
         n = 0
@@ -567,6 +614,38 @@ class DeviceScene:
         """Asynchronous closest-point queries on device buffers (n x 16 B points, n x 32 B results)
         on ``stream`` (rtg_closest_points_device)."""
         _check(lib().rtg_closest_points_device(self._s, points_ptr or None, n, 0, out_ptr or None, stream or None))
+
+    def crossings(self, rays, coherent: bool = False):
+        """How many surfaces each RAY_DTYPE ray meets with 0 < t < tmax -- every one, with no bound
+        on their number -- and at how many of them it goes against the geometric normal, on host
+        arrays (rtg_count_crossings; synchronous): a CROSSINGS_DTYPE array.  ``count & 1`` is the
+        parity test, ``count - entering`` the leaving hits.  ``coherent`` is accepted and ignored.
+        Bit for bit HostScene.crossings."""
+        return _query_crossings(lib().rtg_count_crossings, self._s, rays, coherent)
+
+    def crossings_device(self, rays_ptr: int, n: int, out_ptr: int, stream: int = 0, coherent: bool = False):
+        """Asynchronous crossing counts on device buffers (n x 32 B rays, n x 8 B results) on
+        ``stream`` (rtg_count_crossings_device)."""
+        _check(lib().rtg_count_crossings_device(self._s, rays_ptr or None, n, _query_flags(False, coherent),
+                                                out_ptr or None, stream or None))
+
+    def signed_distance(self, points, direction=None):
+        """closest() and, in the same launch, one unbounded crossing walk from each point along
+        ``direction`` (three floats; None: the library's default, which lies in no coordinate or
+        diagonal plane), on host arrays (rtg_signed_distance_points; synchronous).  The
+        NEAREST_DTYPE record is closest()'s with the crossing count in ``pad0`` and, on a hit with an
+        odd count, a negative ``dist`` (-0.0 on the surface).  Inside means inside an odd number of
+        closed surfaces; on an open surface choose a direction that leaves through it (a height
+        field: (0, 0, 1) answers "below the terrain").  Bit for bit HostScene.signed_distance."""
+        return _query_signed_distance(lib().rtg_signed_distance_points, self._s, points, direction)
+
+    def signed_distance_device(self, points_ptr: int, n: int, out_ptr: int, direction=None, stream: int = 0):
+        """Asynchronous signed-distance queries on device buffers (n x 16 B points, n x 32 B
+        results) on ``stream`` (rtg_signed_distance_points_device); ``direction`` is host data."""
+        d = _direction(direction)
+        _check(lib().rtg_signed_distance_points_device(self._s, points_ptr or None, n,
+                                                       None if d is None else d.ctypes.data, 0, out_ptr or None,
+                                                       stream or None))
 
     def camera_rays(self, camera: int = 0, rows=(0, 0), sample: int = 0, seed: int = 0x5EED) -> np.ndarray:
         """The rays render() traces for ``camera`` at sample index ``sample`` and ``seed``, rows

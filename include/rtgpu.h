@@ -581,8 +581,8 @@ typedef struct { float dist; int32_t object, face, pad0;       /* 32 B: two 16-b
  *    no buffer.  A null scene, or a null buffer with n > 0, is RTG_ERR_INVALID.  The refusal of
  *    an ellipsoid scene comes before the n == 0 rule: such a scene answers RTG_ERR_UNSUPPORTED for
  *    every n, 0 included (the argument errors above come before both).
- *  - Out of scope: the sign of the distance, the k nearest primitives, ellipsoids, a motion-blur
- *    time, a packet walk. */
+ *  - Out of scope: the k nearest primitives, ellipsoids, a motion-blur time, a packet walk.  The
+ *    sign of the distance is rtg_signed_distance_points' (below). */
 
 /* Device-resident buffers on `stream`; asynchronous, allocates nothing and touches no render
  * state.  A multi-device scene answers on its first replica.  Works on clones and after
@@ -595,6 +595,87 @@ int rtg_closest_points(rtg_scene* scene, const rtg_point* points, int64_t n, uin
  * for bit.  RTG_ERR_INVALID for a description without nodes (RTG_LOAD_DEVICE_BVH). */
 int rtg_desc_closest_points(const rtg_scene_desc* desc, const rtg_point* points, int64_t n, uint32_t flags,
                             rtg_nearest* out);
+
+/* ------------------------------------------------------------------------- */
+/* Crossing counts and signed distances: how many surfaces a ray meets, with  */
+/* no bound on their number, and the closest-point distance signed by the     */
+/* parity of that count.  Added symbols and one type only -- RTG_ABI_VERSION  */
+/* stays 6.                                                                   */
+/* ------------------------------------------------------------------------- */
+/* 8 B: one 8-byte store per ray */
+typedef struct { int32_t count; int32_t entering; } rtg_crossings;
+
+/* Semantics of a crossing count (no reference code stands behind it: rtg_desc_count_crossings'
+ * host walk defines it, the device repeats it bit for bit):
+ *  - The walk is rtg_trace_rays_multi's with a minT that is tmax from start to end: the same object
+ *    loop, the same group and instance world-box tests, the same moved-origin rule for a
+ *    motion-blurred instance whose world box is missed, the same box, face and sphere arithmetic.
+ *    Nothing is kept, so nothing is culled: every hit with t > 0 && t < tmax is counted, whatever
+ *    their number.  Large leaves are tested face by face like any other.
+ *  - count: the number of accepted hits.  A sphere gives both roots; a double root counts once (the
+ *    second root counts only if it differs from the first).  Coincident surfaces are all counted.
+ *    RTG_OBJF_SHADOW_SKIP objects count.  time is the motion-blur time.  Consequence: wherever
+ *    rtg_trace_rays_multi with k = 8 reports counts[i] < 8, count equals it exactly (that walk's minT
+ *    never left tmax either); where it reports 8, count >= 8.
+ *  - entering: the number of counted hits at which the ray goes against the geometric normal.  At a
+ *    face: (dx nx + dy ny) + dz nz < 0 in float, d the ray's direction in the object's local space
+ *    (the walk's own ray) and n the face's normal (rtg_face.n, what rtg_trace_rays' `normals` is
+ *    built from); the sign is the same in world space, mirrored transforms included.  At a sphere
+ *    the root (-b - delta) / a enters and the other leaves (a double root enters).  A counted hit
+ *    that is not entering is leaving: count - entering is a winding-style test on consistently
+ *    oriented meshes, count & 1 the parity test.
+ *  - tmax <= 0, a NaN tmax and non-finite rays give whatever the comparisons give: the promise is
+ *    device == host, as for the other queries.
+ *  - flags: RTG_QUERY_COHERENT is accepted and ignored.  RTG_QUERY_ANY_HIT or an unknown bit is
+ *    RTG_ERR_INVALID.  n == 0 is RTG_OK; n above INT32_MAX or a null scene / buffer is
+ *    RTG_ERR_INVALID.
+ *  - Cost: an unbounded ray visits every box it pierces and tests every face in them; a caller
+ *    who knows a bound should give it as tmax.
+ *  - A ray through an edge or a vertex shared by faces may count it once or twice, as the face
+ *    test's comparisons fall: the host walk decides, and the device agrees with it. */
+
+/* Device-resident buffers on `stream`: asynchronous, allocates nothing and touches no render
+ * state.  A multi-device scene answers on its first replica.  Works on clones and after
+ * rtg_scene_update. */
+int rtg_count_crossings_device(rtg_scene* scene, const rtg_ray* d_rays, int64_t n, uint32_t flags,
+                               rtg_crossings* d_out, void* stream);
+/* Same on host buffers (synchronous; the scene's query scratch and its own stream). */
+int rtg_count_crossings(rtg_scene* scene, const rtg_ray* rays, int64_t n, uint32_t flags, rtg_crossings* out);
+/* Host only, no device: the walk that defines the query.  RTG_ERR_INVALID for a description
+ * without nodes (RTG_LOAD_DEVICE_BVH). */
+int rtg_desc_count_crossings(const rtg_scene_desc* desc, const rtg_ray* rays, int64_t n, uint32_t flags,
+                             rtg_crossings* out);
+
+/* Signed distances: per point the closest-point query, then one crossing walk from the point.
+ *  - The closest point: exactly rtg_closest_points' -- same candidates, same tie rule, same miss
+ *    record, same ellipsoid refusal.
+ *  - The crossing walk above on the ray (origin = the point, direction = dir, tmax = INFINITY,
+ *    time = 0).
+ *  - The record is rtg_closest_points' with two differences.  pad0 is the crossing count.  On a hit
+ *    with an odd count dist has its sign bit set: -sqrtf(best_d2), which is -0.0f on the surface.
+ *    On a miss dist stays max_dist's own bits and pad0 still carries the count: a caller baking a
+ *    narrow band still learns the side.  A point with a non-finite coordinate gives the
+ *    closest-point miss record with pad0 = 0 (no walk is run).
+ *  - dir: a host pointer to three floats in all three entry points (the device path hands it to the
+ *    kernel by value).  NULL selects (0.8213f, 0.4402f, 0.3628f), which lies in no coordinate or
+ *    diagonal plane.  It need not be of unit length: only counts are read.  A non-finite or
+ *    all-zero dir is RTG_ERR_INVALID.
+ *  - What the sign means: the parity of the surfaces crossed along dir.  That is "inside" for
+ *    closed surfaces (inside an odd number of them: the cavity of a hollow shell is outside), and
+ *    for an open surface along a direction that leaves through it: on a height field dir =
+ *    (0, 0, 1) answers "below the terrain".  A ray through an edge or a vertex may count it once or
+ *    twice (the host walk decides); pad0 lets a caller see the count and ask again with another
+ *    dir.  For consistently oriented meshes count - entering is available from
+ *    rtg_count_crossings.
+ *  - flags must be 0.  n and null rules as for rtg_closest_points, the ellipsoid refusal
+ *    (RTG_ERR_UNSUPPORTED) before the n == 0 rule and after the argument errors, dir's among them.
+ *  - Out of scope: generalised winding numbers, a motion-blur time, a packet walk. */
+int rtg_signed_distance_points_device(rtg_scene* scene, const rtg_point* d_points, int64_t n, const float dir[3],
+                                      uint32_t flags, rtg_nearest* d_out, void* stream);
+int rtg_signed_distance_points(rtg_scene* scene, const rtg_point* points, int64_t n, const float dir[3],
+                               uint32_t flags, rtg_nearest* out);
+int rtg_desc_signed_distance_points(const rtg_scene_desc* desc, const rtg_point* points, int64_t n,
+                                    const float dir[3], uint32_t flags, rtg_nearest* out);
 
 /* ------------------------------------------------------------------------- */
 /* Surface queries: what the renderer knows about the point a ray hits --     */

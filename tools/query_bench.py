@@ -13,7 +13,7 @@ renders: RTG_FRAME_KERNEL=0 splits the sample pass into k_primary + k_shade_shad
 RTG_RENDER_EXACT_SHADOW gives k_shadow with the reference walk).  k_primary is the yardstick of
 (a): the same walk on the same rays, with a 32-byte ray read in place of ray generation.
 
-    python tools/query_bench.py [--launches 50] [--reps 3] [--out FILE] [--sections query,radiance,surface,update,multi,closest]
+    python tools/query_bench.py [--launches 50] [--reps 3] [--out FILE] [--sections query,radiance,surface,update,multi,closest,crossings,sdf]
 
 The radiance section (rtg_radiance_rays_device, DeviceScene.radiance_device) runs on the same
 height field and on the path-tracing fixture tests/golden/scenes/pt_cornell.xml at its own size:
@@ -56,6 +56,18 @@ field, about two million points a launch, in Gpoints/s:
 each with max_dist = inf and with a radius of four mean cell sizes.  A 65 536-point sample of every
 case is checked against the host walk bit for bit before anything is timed.  The library is the
 one rtgpu loads ($RTGPU_LIB for an experiment's build, as in the seed-pass comparison of DESIGN.md).
+
+The crossings section (rtg_count_crossings_device, DeviceScene.crossings_device) runs on the same
+height field: the camera's unbounded rays, in pixel order and permuted, through crossings_device and
+through trace_multi_device with k = 8 and counts.  All but a few hundred of the two million rays
+(grazing ones near the horizon) hold fewer than 8 hits there, so on those both walks visit the same
+boxes and the counts are equal (asserted; the others count at least 8); the condition is crossings
+rate >= the k = 8 multi-hit rate of the same run.
+
+The sdf section (rtg_signed_distance_points_device, DeviceScene.signed_distance_device) runs on the
+closest section's grid (g) with dir = (0, 0, 1), unbounded and within four cells: the fused launch
+against closest_device then crossings_device on the same points.  The condition is fused time <= the
+sum of the two launches' times in the same run.
 """
 import argparse
 import os
@@ -529,6 +541,176 @@ def closest_main(args):
     return lines
 
 
+def _timed(cases, run, args):
+    """ms per launch of every case: warm-up, then --reps interleaved repetitions of --launches launches."""
+    import torch
+    for key in cases:
+        run(key, args.warmup)
+    torch.cuda.synchronize()
+    ms = {key: [] for key in cases}
+    for _ in range(args.reps):
+        for key in cases:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            run(key, args.launches)
+            e1.record()
+            e1.synchronize()
+            ms[key].append(e0.elapsed_time(e1) / args.launches)
+    return ms
+
+
+def crossings_main(args):
+    """Crossing counts (rtg_count_crossings_device) on the headline height field: lines of text."""
+    import torch
+
+    import rtgpu
+    import scenes
+
+    tmp = tempfile.mkdtemp(prefix="query_bench_")
+    xml = scenes.synthetic_heightfield(tmp, K=args.K, width=args.width, height=args.height)
+    os.chdir(tmp)
+    hs = rtgpu.HostScene(xml)
+    ds = rtgpu.DeviceScene(hs, 0)
+    n = args.width * args.height
+    dev = torch.device("cuda:0")
+    st = torch.cuda.current_stream().cuda_stream
+    rays = torch.empty((n, 8), dtype=torch.float32, device=dev)
+    ds.camera_rays_device(rays.data_ptr(), stream=st)
+    torch.cuda.synchronize()
+    g = torch.Generator(device="cpu").manual_seed(1234)
+    sets = {"pixel order": rays, "permuted": rays[torch.randperm(n, generator=g).to(dev)].contiguous()}
+    hits = torch.empty((n, 8, 4), dtype=torch.int32, device=dev)
+    cnt = torch.empty((n,), dtype=torch.int32, device=dev)
+    out = torch.empty((n, 2), dtype=torch.int32, device=dev)
+    cases = [(kind, which) for which in sets for kind in ("crossings", "multi k = 8 + counts")]
+
+    def run(key, reps):
+        kind, which = key
+        buf = sets[which]
+        for _ in range(reps):
+            if kind == "crossings":
+                ds.crossings_device(buf.data_ptr(), n, out.data_ptr(), stream=st)
+            else:
+                ds.trace_multi_device(buf.data_ptr(), n, 8, hits.data_ptr(), cnt.data_ptr(), stream=st)
+
+    # the answers first: the multi-hit counts (equal wherever that walk holds fewer than 8 hits) and a sample of the host walk
+    most = {}
+    for which, buf in sets.items():
+        run(("crossings", which), 1)
+        run(("multi k = 8 + counts", which), 1)
+        torch.cuda.synchronize()
+        full = cnt >= 8
+        assert torch.equal(out[:, 0][~full], cnt[~full]) and bool((out[:, 0][full] >= 8).all()), which
+        pick = np.random.default_rng(1234).choice(n, 65536, replace=False)
+        want = hs.crossings(buf.cpu().numpy().view(rtgpu.RAY_DTYPE).reshape(-1)[pick])
+        assert out.cpu().numpy()[pick].tobytes() == want.tobytes(), (which, "device != host walk")
+        most[which] = (int(out[:, 0].max()), float(out[:, 0].float().mean()), int(full.sum()))
+    ms = _timed(cases, run, args)
+    lines = [f"crossings: synthetic_heightfield K={args.K} {args.width}x{args.height}, {n} unbounded camera rays, {args.launches} "
+             f"launches x {args.reps} interleaved repetitions, device {torch.cuda.get_device_name(0)} (counts equal the k = 8 "
+             f"multi-hit counts on every ray that holds fewer than 8 hits, all but {most['pixel order'][2]}; 65 536 rays of each "
+             f"order equal the host walk bit for bit; hits per ray: mean {most['pixel order'][1]:.3f}, most {most['pixel order'][0]})",
+             f"{'case':44s} {'ms (median)':>12s} {'min':>8s} {'max':>8s} {'Grays/s':>9s}"]
+    for key in cases:
+        v = ms[key]
+        lines.append(f"{key[0] + ', ' + key[1]:44s} {np.median(v):12.4f} {min(v):8.4f} {max(v):8.4f} {n / np.median(v) / 1e6:9.3f}")
+    for which in sets:
+        c, m = np.median(ms["crossings", which]), np.median(ms["multi k = 8 + counts", which])
+        lines.append(f"{which}: crossings rate / multi-hit k = 8 rate = {m / c:.3f} (condition: >= 1)")
+    spread = lambda v: (max(v) - min(v)) / np.median(v) * 100
+    lines.append("spread over the repetitions: " + ", ".join(f"{spread(ms[key]):.1f} %" for key in cases))
+    return lines
+
+
+def sdf_main(args):
+    """Signed distances (rtg_signed_distance_points_device) on the headline height field against
+    closest_device then crossings_device on the same points: lines of text."""
+    import torch
+
+    import rtgpu
+    import scenes
+
+    tmp = tempfile.mkdtemp(prefix="query_bench_")
+    xml = scenes.synthetic_heightfield(tmp, K=args.K, width=args.width, height=args.height)
+    os.chdir(tmp)
+    hs = rtgpu.HostScene(xml)
+    ds = rtgpu.DeviceScene(hs, 0)
+    rng = np.random.default_rng(1234)
+    rays = ds.camera_rays()
+    hits = ds.trace(rays)
+    ok = hits["object"] >= 0
+    o = np.stack([rays["ox"], rays["oy"], rays["oz"]], 1)[ok]
+    d = np.stack([rays["dx"], rays["dy"], rays["dz"]], 1)[ok]
+    hit_xyz = o + d * hits["t"][ok][:, None]
+    # the closest section's grid: jittered 512 x 512 x 8 through the box of the camera's hit points
+    lo, hi = hit_xyz.min(0).astype(np.float64), hit_xyz.max(0).astype(np.float64)
+    hi[2] += 0.05 * (hi[0] - lo[0])
+    gx, gy, gz = 512, 512, 8
+    cell = (hi - lo) / (gx, gy, gz)
+    zz, yy, xx = np.meshgrid(np.arange(gz), np.arange(gy), np.arange(gx), indexing="ij")
+    grid = np.stack([xx, yy, zz], -1).reshape(-1, 3)
+    grid = (lo + (grid + rng.random(grid.shape)) * cell).astype(np.float32)
+    radius = float(4.0 * np.sqrt((hi[0] - lo[0]) * (hi[1] - lo[1]) / (args.K / 2)))
+    up = (0.0, 0.0, 1.0)                         # the field's heights are along z
+    n = len(grid)
+    dev = torch.device("cuda:0")
+    st = torch.cuda.current_stream().cuda_stream
+    up_rays = rtgpu.make_rays(grid, np.tile(np.array(up, np.float32), (n, 1)))
+    d_rays = torch.from_numpy(up_rays.view(np.float32).reshape(-1, 8).copy()).to(dev)
+    d_cross = torch.empty((n, 2), dtype=torch.int32, device=dev)
+    d_out = torch.empty((n, 8), dtype=torch.int32, device=dev)
+    bufs, below = {}, {}
+    for label, md in (("max_dist = inf", np.inf), ("max_dist = %.4g" % radius, radius)):
+        pts = rtgpu.make_points(grid, md)
+        d_pts = torch.from_numpy(pts.view(np.float32).reshape(-1, 4).copy()).to(dev)
+        ds.signed_distance_device(d_pts.data_ptr(), n, d_out.data_ptr(), direction=up, stream=st)
+        torch.cuda.synchronize()
+        got = d_out.cpu().numpy()
+        pick = rng.choice(n, 65536, replace=False)
+        assert got[pick].tobytes() == hs.signed_distance(pts[pick], up).tobytes(), (label, "device != host walk")
+        # the two launches give the same record: closest's with the count and the sign put in
+        ds.closest_device(d_pts.data_ptr(), n, d_out.data_ptr(), stream=st)
+        ds.crossings_device(d_rays.data_ptr(), n, d_cross.data_ptr(), stream=st)
+        torch.cuda.synchronize()
+        two = d_out.cpu().numpy().view(rtgpu.NEAREST_DTYPE).reshape(-1).copy()
+        count = d_cross.cpu().numpy()[:, 0]
+        two["pad0"] = count
+        flip = (two["object"] >= 0) & ((count & 1) == 1)
+        two["dist"][flip] = -two["dist"][flip]
+        assert two.tobytes() == got.tobytes(), (label, "fused != closest + crossings")
+        below[label] = float((count & 1).mean())
+        bufs[label] = d_pts
+    cases = [(kind, label) for label in bufs for kind in ("signed_distance (fused)", "closest", "crossings")]
+
+    def run(key, reps):
+        kind, label = key
+        d_pts = bufs[label]
+        for _ in range(reps):
+            if kind == "closest":
+                ds.closest_device(d_pts.data_ptr(), n, d_out.data_ptr(), stream=st)
+            elif kind == "crossings":
+                ds.crossings_device(d_rays.data_ptr(), n, d_cross.data_ptr(), stream=st)
+            else:
+                ds.signed_distance_device(d_pts.data_ptr(), n, d_out.data_ptr(), direction=up, stream=st)
+
+    ms = _timed(cases, run, args)
+    lines = [f"sdf: synthetic_heightfield K={args.K}, {n} points of the closest section's grid, dir = (0, 0, 1), {args.launches} "
+             f"launches x {args.reps} interleaved repetitions, device {torch.cuda.get_device_name(0)} (65 536 points of each "
+             f"case equal the host walk bit for bit; the fused record equals closest + crossings on every point; "
+             f"{below['max_dist = inf']:.3f} of the points are below the terrain)",
+             f"{'case':48s} {'ms (median)':>12s} {'min':>8s} {'max':>8s} {'Gpoints/s':>10s}"]
+    for key in cases:
+        v = ms[key]
+        lines.append(f"{key[0] + ', ' + key[1]:48s} {np.median(v):12.4f} {min(v):8.4f} {max(v):8.4f} {n / np.median(v) / 1e6:10.3f}")
+    for label in bufs:
+        f = np.median(ms["signed_distance (fused)", label])
+        two = np.median(ms["closest", label]) + np.median(ms["crossings", label])
+        lines.append(f"{label}: fused {f:.4f} ms, closest + crossings {two:.4f} ms, ratio {f / two:.3f} (condition: <= 1)")
+    spread = lambda v: (max(v) - min(v)) / np.median(v) * 100
+    lines.append("spread over the repetitions: " + ", ".join(f"{spread(ms[key]):.1f} %" for key in cases))
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--setups", type=int, default=9, help="update section: calls per set-up time")
@@ -556,6 +738,10 @@ def main():
         text += multi_main(args)
     if "closest" in sections:
         text += closest_main(args)
+    if "crossings" in sections:
+        text += crossings_main(args)
+    if "sdf" in sections:
+        text += sdf_main(args)
     text = "\n".join(text)
     print(text)
     if out:
